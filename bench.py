@@ -15,12 +15,17 @@ Honesty rules applied here:
     launches for >= --settle-s seconds so a short W starts the region at the loaded clock; the
     line reports the settle ("settle") and W ("warmup") as run;
   * roofline.achieved = bytes per launch / (HIP-event time of the timed region on the launch
-    stream / K); digests of the last step are spot-checked against hashlib.
+    stream / K).
+
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) sets up, warms up, times the K steps, writes
+the last step's results under --dump-outputs DIR if given, and prints the line.  --full adds the
+other legs: the last step's results checked (hashlib, the oracle, round trips), cpu_baseline,
+pcie_inclusive, the cfg5 sub-object, --two-stream.
 
 Other workloads for DESIGN.md: --config 1 (one 1 MiB buffer through the compat BRB_MD5* calls on
 the CPU, no GPU), --config 3 (1 Mi x 64 B MD5), --config 4 (1 GiB Blowfish enc+dec), --op sha1.
-Every digest line also carries a "cfg5" object: 1 048 576 x 1500 B records per GPU (exactly
-BASELINE cfg5, 8 388 608 records, at --gpus 8).  Run `python bench.py --help`.
+With --full the cfg2 MD5 line also carries a "cfg5" object: 1 048 576 x 1500 B records per GPU
+(exactly BASELINE cfg5, 8 388 608 records, at --gpus 8).  Run `python bench.py --help`.
 """
 from __future__ import annotations
 
@@ -93,7 +98,70 @@ def parse():
                     help="enqueue a tiny spin kernel (at::cuda spin_kernel) right before and right after each "
                          "timed region, outside the timing, so a rocprofv3 kernel trace can select exactly the "
                          "timed dispatches (tools/collect_profiles.py)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: check the last step's results (hashlib, the oracle, round trips) "
+                         "and run the other legs (cpu_baseline, pcie_inclusive, the cfg5 sub-object, --two-stream); "
+                         "each leg's --no-* switch still drops it.  Off: set up, warm up, time the K steps, print")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last timed step computed (the arrays a caller of "
+                         "the step receives) as DIR/<name>.npy, float32 / float64, at most 64 MB in all (a fixed, "
+                         "seeded sample of a larger array).  The inputs are seeded: same arguments, same inputs")
+    args = ap.parse_args()
+    if not args.full:             # a plain run does only what the headline needs
+        args.no_cpu_baseline = args.no_pcie = args.no_cfg5 = True
+        args.two_stream = False
+    if args.dump_outputs and args.op == "batcher":
+        ap.error("--dump-outputs: the batcher line runs in a child process that keeps its buffers")
+    return args
+
+
+# ------------------------------------------------------------------------------------------------
+DUMP_BYTES = 60 * 1000 * 1000     # of .npy data per run: under the 64 MB a dump may take, headers included
+DUMP_SEED = 0x5EED0D0D            # of the sample taken from an array over its share
+DUMPED = {}                       # keep_outputs(): name -> float32 / float64 array
+
+
+def keep_outputs(args, rank, world, **arrays):
+    """--dump-outputs: keep what the last timed step computed, called right after the timed region
+    (before any other leg touches the buffers).  `arrays`: name -> torch tensor or numpy array, as
+    the step's caller holds them.  Bytes become float32; 2- and 4-byte integers float64 (exact);
+    8-byte words are kept as their bytes (a float64 does not hold 64 bits).  Each array may take an
+    equal share of DUMP_BYTES; a larger one is sampled at DUMP_SEED's sorted positions (the same
+    positions in every run of the same shape), on the device when it lives there."""
+    if not args.dump_outputs:
+        return
+    import numpy as np
+    share = DUMP_BYTES // (world * max(1, len(arrays)))
+    for name, a in arrays.items():
+        on_dev = not isinstance(a, np.ndarray)
+        if on_dev:
+            import torch
+        flat = a.reshape(-1)
+        size = a.element_size() if on_dev else a.dtype.itemsize
+        words = size == 8
+        if words:
+            flat, size = flat.view(torch.uint8 if on_dev else np.uint8), 1
+        n = flat.numel() if on_dev else flat.size
+        out_t = np.float32 if size == 1 else np.float64
+        keep = share // np.dtype(out_t).itemsize
+        sampled = n > keep
+        if sampled:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, n, keep))
+            flat = flat[torch.from_numpy(idx).to(flat.device)] if on_dev else flat[idx]
+        if on_dev:
+            flat = flat.cpu().numpy()
+        flat = flat.astype(out_t)
+        DUMPED[name if world == 1 else f"{name}_rank{rank}"] = \
+            flat if sampled or words else flat.reshape(tuple(a.shape))
+
+
+def write_outputs(args):
+    if not args.dump_outputs:
+        return
+    import numpy as np
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    for name, a in DUMPED.items():
+        np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
 
 
 def relaunch_distributed(args) -> None:
@@ -328,7 +396,9 @@ def issue_compute(path, key, launch_s, dispatches=1):
 def main():
     args = parse()
     if args.config == 1:          # plumbing, no GPU (BASELINE cfg1)
-        print(json.dumps(bench_cfg1(args)), flush=True)
+        result = bench_cfg1(args)
+        write_outputs(args)
+        print(json.dumps(result), flush=True)
         return
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if args.gpus > 1 and "RANK" not in os.environ:
@@ -401,6 +471,7 @@ def main():
         result = bench_blowfish(args, cfg, rank, world, dev, stream, barrier, max_over_ranks, log)
     else:
         result = bench_digest(args, cfg_id, cfg, rank, world, dev, stream, barrier, max_over_ranks, log)
+    write_outputs(args)
     if rank == 0:
         if NOTES:
             result["notes"] = NOTES
@@ -582,9 +653,13 @@ def bench_digest(args, cfg_id, cfg, rank, world, dev, stream, barrier, max_over_
         # (its digest check runs after the headline's timed region: no idle gap between the legs)
     batch_bytes = host.nbytes
     n_rot = max(2, math.ceil(640e6 / batch_bytes)) if batch_bytes < 2.5 * L3_BYTES else 1
-    bufs = [torch.from_numpy(host).to(dev)]
-    for _ in range(n_rot - 1):
-        bufs.append(bufs[0].clone())
+    # the rotation copies lie in ONE device allocation.  With the cfg5 leg before them they always did
+    # (the caching allocator carves them out of that leg's freed 1.57 GB block); a plain run without
+    # the leg gets the same layout this way.  One allocation per copy measured 0.7-1.2 % slower per
+    # launch (K = 2000, interleaved: 20.44 against 20.29 us, and 21.70 against 21.42 us on another box)
+    arena = torch.empty((n_rot, batch_bytes), dtype=torch.uint8, device=dev)
+    arena[:] = torch.from_numpy(host).to(dev)
+    bufs = [arena[i] for i in range(n_rot)]
     n_streams = max(1, args.streams)
     outs = [torch.empty((n_rank, width), dtype=torch.uint8, device=dev) for _ in range(max(2, n_streams) + 1)]
     torch.cuda.synchronize()
@@ -616,6 +691,7 @@ def bench_digest(args, cfg_id, cfg, rank, world, dev, stream, barrier, max_over_
     wall, ev_s = timed_steps(lambda k, s, j: launch_raw(k + n_warm, s, j), n_steps, main_streams,
                              barrier, max_over_ranks, torch)
     all_k_s = LAST_ALL_K_S
+    keep_outputs(args, rank, world, digests=outs[(n_steps - 1) % len(main_streams)])
     if cfg5 is not None:
         cfg5_verify()
     wall2 = None
@@ -624,11 +700,12 @@ def bench_digest(args, cfg_id, cfg, rank, world, dev, stream, barrier, max_over_
         wall2, _ = timed_steps(launch_raw, n_steps, side[:2], barrier, max_over_ranks, torch)
     out = outs[0]
 
-    # spot-check the last step's digests against hashlib (stdlib, independent of this repo)
-    got = out.cpu().numpy()
-    h = hashlib.md5 if args.op == "md5" else hashlib.sha1
-    for i in list(np.random.default_rng(rank).integers(0, n_rank, 32)) + [0, n_rank - 1]:
-        assert got[i].tobytes() == h(host[i * L:(i + 1) * L].tobytes()).digest(), f"digest mismatch at {i}"
+    if args.full:
+        # spot-check the last step's digests against hashlib (stdlib, independent of this repo)
+        got = out.cpu().numpy()
+        h = hashlib.md5 if args.op == "md5" else hashlib.sha1
+        for i in list(np.random.default_rng(rank).integers(0, n_rank, 32)) + [0, n_rank - 1]:
+            assert got[i].tobytes() == h(host[i * L:(i + 1) * L].tobytes()).digest(), f"digest mismatch at {i}"
 
     total_bytes = n_global * L * n_steps
     gib_s = total_bytes / wall / 2**30
@@ -678,7 +755,7 @@ def bench_digest(args, cfg_id, cfg, rank, world, dev, stream, barrier, max_over_
             "note": "same K steps alternating over 2 HIP streams (2 batches in flight)"}
     if world == 1 and not args.no_pcie:
         result["pcie_inclusive"] = bench_pcie_digest(fn, host, L, n_rank, width, log)
-    del bufs, outs
+    del bufs, outs, arena
     torch.cuda.empty_cache()
     if cfg5 is not None:
         result["cfg5"] = cfg5
@@ -856,12 +933,14 @@ def bench_blowfish(args, cfg, rank, world, dev, stream, barrier, max_over_ranks,
 
     n_warm, n_steps = warm_up(args, launch, [stream], torch, max_over_ranks)
     wall, ev_s = timed_steps(launch, n_steps, [stream], barrier, max_over_ranks, torch)
-    assert torch.equal(d, d0), "Blowfish round trip did not restore the plaintext"
-    # one encrypt-only check against the oracle on a sample record
-    brb.blowfish_encrypt_batch(cdev, d, n_blocks)
-    wpr = cfg["rec_len"] // 8
-    got = d[:wpr].cpu().numpy().view(np.uint64)
-    assert np.array_equal(got, oracle.bf_ecb(oracle.bf_init(workload.CFG4_KEY), w[:wpr].copy()))
+    keep_outputs(args, rank, world, words=d)
+    if args.full:
+        assert torch.equal(d, d0), "Blowfish round trip did not restore the plaintext"
+        # one encrypt-only check against the oracle on a sample record
+        brb.blowfish_encrypt_batch(cdev, d, n_blocks)
+        wpr = cfg["rec_len"] // 8
+        got = d[:wpr].cpu().numpy().view(np.uint64)
+        assert np.array_equal(got, oracle.bf_ecb(oracle.bf_init(workload.CFG4_KEY), w[:wpr].copy()))
     step_s = ev_s
     plain = n_words * 8
     result = {
@@ -997,23 +1076,28 @@ def bench_cfg1(args):
 
     warm = args.warmup if args.warmup is not None else 1
     steps, dt = timed(compat, max(1.0, args.cpu_seconds / 2), args.steps, warm)
-    assert bytes(ctx.digest).hex() == want, "compat MD5 of the cfg1 buffer differs from the golden digest"
-    o_steps, o_dt = timed(lambda: oracle.md5(buf), max(1.0, args.cpu_seconds / 2))
-    assert oracle.md5(buf).hex() == want
+    import numpy as np
+    keep_outputs(args, 0, 1, digest=np.frombuffer(bytes(ctx.digest), np.uint8))
     rate = len(buf) * steps / dt / 2**30
-    o_rate = len(buf) * o_steps / o_dt / 2**30
-    return {"metric": "GiB/s of MD5 over one 1 MiB buffer through the compat BRB_MD5Init/UpdateBig/Final (cfg1, CPU)",
+    line = {"metric": "GiB/s of MD5 over one 1 MiB buffer through the compat BRB_MD5Init/UpdateBig/Final (cfg1, CPU)",
             "value": round(rate, 3), "unit": "GiB/s", "n_gpus": 0, "steps": steps, "warmup": max(1, warm),
             "ms_per_step": round(dt / steps * 1e3, 4), "higher_is_better": True, "scaling": "none",
             "vs_baseline": None, "dtype": "u32", "data": "synthetic (SURVEY §8(d) generator, seed 0x5EED0001)",
             "config": {"workload": cfg["name"], "op": "BRB_MD5Init + BRB_MD5UpdateBig + BRB_MD5Final (compat, host C)",
                        "record_bytes": len(buf), "parallelism": "one CPU thread"},
-            "digest": bytes(ctx.digest).hex(), "golden_match": True,
+            "digest": bytes(ctx.digest).hex(),
             "roofline": None,
-            "cpu_baseline": {"value": round(o_rate, 3), "unit": "GiB/s", "cores": 1, "kind": "port",
-                             "sample": f"oracle/brb_oracle.c MD5 of the same 1 MiB buffer, {o_steps} passes"},
             "note": "cfg1 is the reference's single-buffer CPU path (SURVEY §8(d)): a serial chain of 16 385 "
                     "compressions, no GPU and no roofline"}
+    if args.full:
+        assert bytes(ctx.digest).hex() == want, "compat MD5 of the cfg1 buffer differs from the golden digest"
+        o_steps, o_dt = timed(lambda: oracle.md5(buf), max(1.0, args.cpu_seconds / 2))
+        assert oracle.md5(buf).hex() == want
+        o_rate = len(buf) * o_steps / o_dt / 2**30
+        line.update({"golden_match": True,
+                     "cpu_baseline": {"value": round(o_rate, 3), "unit": "GiB/s", "cores": 1, "kind": "port",
+                                      "sample": f"oracle/brb_oracle.c MD5 of the same 1 MiB buffer, {o_steps} passes"}})
+    return line
 
 
 # ------------------------------------------------------------------------------------------------
@@ -1073,7 +1157,13 @@ def bench_rc4(args, rank, world, dev, stream, barrier, max_over_ranks, log):
     n_warm, n_steps = warm_up(args, launch, [stream], torch, max_over_ranks)
     wall, ev_s = timed_steps(lambda k, s, j: launch(k + n_warm, s, j), n_steps, [stream], barrier,
                              max_over_ranks, torch)
-    if args.op == "rc4md5":
+    # (the RC4 states advance with every launch, the untimed ones too: a dump repeats from run to run
+    # only when their number is fixed, --warmup W --settle-s 0)
+    if args.op == "rc4":
+        keep_outputs(args, rank, world, data=bufs[(n_warm + n_steps - 1) % n_rot], states=wst)
+    else:
+        keep_outputs(args, rank, world, frames=frames, valid=valid, write_states=wst, read_states=rst)
+    if args.op == "rc4md5" and args.full:
         assert int(valid.sum()) == n, "a frame failed validation"
         assert torch.equal(wst, rst), "write and read states diverged"
         fr = frames[: 2 * (L + H)].cpu().numpy()
@@ -1190,11 +1280,13 @@ def bench_var(args, rank, world, dev, stream, barrier, max_over_ranks, log):
     n_warm, n_steps = warm_up(args, launch, [stream], torch, max_over_ranks)
     wall, ev_s = timed_steps(lambda k, s, j: launch(k + n_warm, s, j), n_steps, [stream], barrier,
                              max_over_ranks, torch)
-    got = out.cpu().numpy()
-    h = hashlib.md5 if args.op == "md5var" else hashlib.sha1
-    for i in list(rng.integers(0, n, 32)) + [0, n - 1]:
-        o, L = int(offs_h[i]), int(lens_h[i])
-        assert got[i].tobytes() == h(host[o:o + L].tobytes()).digest(), f"digest mismatch at {i}"
+    keep_outputs(args, rank, world, digests=out)
+    if args.full:
+        got = out.cpu().numpy()
+        h = hashlib.md5 if args.op == "md5var" else hashlib.sha1
+        for i in list(rng.integers(0, n, 32)) + [0, n - 1]:
+            o, L = int(offs_h[i]), int(lens_h[i])
+            assert got[i].tobytes() == h(host[o:o + L].tobytes()).digest(), f"digest mismatch at {i}"
     step_s = ev_s
     payload = int(lens_h.sum())
     name = "BRB_MD5Batch" if args.op == "md5var" else "BrbSha1_Batch"
@@ -1339,6 +1431,14 @@ def bench_f4(args, rank, world, dev, stream, barrier, max_over_ranks, log):
                              max_over_ranks, torch)
     torch.cuda.synchronize()
     if args.op == "metadata":
+        keep_outputs(args, rank, world, info=info)
+    elif args.op == "md5seg":
+        keep_outputs(args, rank, world, digests=digs)
+    else:
+        keep_outputs(args, rank, world, text=text, records=back, record_lens=olens)
+    if not args.full:
+        pass                                   # a plain run checks nothing
+    elif args.op == "metadata":
         got = info.cpu().numpy().reshape(-1).view(brb.METADATA_INFO_DTYPE)
         assert (got["error_code"] == 7).all() and (got["item_count"] == 4).all(), "a pack failed to unpack"
         assert (got["cur_offset"] == P_SZ).all()
@@ -1429,19 +1529,12 @@ def bench_batcher(args, rank, world, log):
         if "error" in r:
             raise SystemExit("batcher_bench: " + r["error"])
         return r
-    r, z, rp, zp, rp4 = run(0), run(1), run(0, 1), run(1, 1), run(0, 1, 4)
+    r = run(0)
     t = r["round_ms_mean"] / 1e3
-    return {"metric": "GiB/s of payload through the receive-loop transform batcher (SURVEY §8 f2, host-inclusive)",
-            "value": r["payload_gib_s"], "unit": "GiB/s", "n_gpus": world, "steps": steps,
-            "warmup": warm, "ms_per_step": round(t * 1e3, 3), "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "u8",
-            "data": "synthetic (peer frames built with the compat BRB_RC4/BRB_MD5 calls outside the timed region)",
-            "config": {"workload": f"f2: {C} connections x (1 frame in + 1 payload out) x 1500 B per round",
-                       "op": "tools/batcher_bench.c: BRB_TransformBatcherRead/Write per buffer + Flush per round",
-                       "parallelism": "single GPU"},
-            "buffers_per_s": r["buffers_per_s"], "round_ms_min": r["round_ms_min"],
-            "submit_ms_median": r["submit_ms_median"],
-            "zero_copy": {"value": z["payload_gib_s"], "unit": "GiB/s", "ms_per_step": z["round_ms_mean"],
+
+    def other_modes():
+        z, rp, zp, rp4 = run(1), run(0, 1), run(1, 1), run(0, 1, 4)
+        return {"zero_copy": {"value": z["payload_gib_s"], "unit": "GiB/s", "ms_per_step": z["round_ms_mean"],
                           "submit_ms_median": z["submit_ms_median"],
                           "op": "BRB_BATCHER_ZERO_COPY: buffers page-locked once (BRB_CryptoGPU_HostRegister), "
                                 "kernels read them and write results over PCIe, no arena copies"},
@@ -1453,7 +1546,19 @@ def bench_batcher(args, rank, world, log):
                                                     "submit_ms_median": rp4["submit_ms_median"]},
                           "unit": "GiB/s",
                           "op": "BRB_BATCHER_PIPELINED: FlushAsync per round, the loop submits round k+1 while "
-                                "the GPU runs round k"},
+                                "the GPU runs round k"}}
+
+    return {"metric": "GiB/s of payload through the receive-loop transform batcher (SURVEY §8 f2, host-inclusive)",
+            "value": r["payload_gib_s"], "unit": "GiB/s", "n_gpus": world, "steps": steps,
+            "warmup": warm, "ms_per_step": round(t * 1e3, 3), "higher_is_better": True, "scaling": "weak",
+            "vs_baseline": None, "dtype": "u8",
+            "data": "synthetic (peer frames built with the compat BRB_RC4/BRB_MD5 calls outside the timed region)",
+            "config": {"workload": f"f2: {C} connections x (1 frame in + 1 payload out) x 1500 B per round",
+                       "op": "tools/batcher_bench.c: BRB_TransformBatcherRead/Write per buffer + Flush per round",
+                       "parallelism": "single GPU"},
+            "buffers_per_s": r["buffers_per_s"], "round_ms_min": r["round_ms_min"],
+            "submit_ms_median": r["submit_ms_median"],
+            **(other_modes() if args.full else {}),
             "note": "step = one round: per-buffer submit (copy into the pinned arena), H2D, open + frame kernels, "
                     "D2H, one callback per buffer"}
 

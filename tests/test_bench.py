@@ -28,6 +28,98 @@ def test_cfg1_line_fields():
     assert FIELDS <= set(d)
     assert d["steps"] == 3 and d["warmup"] == 1 and d["value"] > 0 and d["higher_is_better"] is True
     assert d["config"]["workload"].startswith("cfg1")
+    assert "cpu_baseline" not in d and "golden_match" not in d      # a plain run: the timed steps only
+
+
+def test_cfg1_full_line_and_dump(tmp_path):
+    """--full adds the golden check and the oracle's rate; --dump-outputs writes the last step's digest."""
+    import numpy as np
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "1", "--steps", "3", "--warmup", "1",
+                          "--full", "--cpu-seconds", "0.2", "--dump-outputs", str(tmp_path / "dump")],
+                         capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    d = json.loads(out.stdout.strip().splitlines()[-1])
+    assert FIELDS <= set(d) and d["steps"] == 3
+    assert d["golden_match"] is True and d["cpu_baseline"]["value"] > 0
+    assert os.listdir(tmp_path / "dump") == ["digest.npy"]
+    got = np.load(tmp_path / "dump" / "digest.npy")
+    assert got.dtype == np.float32 and bytes(got.astype(np.uint8)).hex() == d["digest"]
+
+
+def _parse(argv, monkeypatch):
+    monkeypatch.setattr(sys, "argv", ["bench.py"] + argv)
+    return bench.parse()
+
+
+def test_plain_run_has_no_other_legs(monkeypatch):
+    """Without --full every other leg is off, whatever else is asked; with it each --no-* still drops its leg."""
+    a = _parse(["--gpus", "1", "--steps", "20", "--warmup", "5", "--two-stream"], monkeypatch)
+    assert (a.full, a.no_cpu_baseline, a.no_pcie, a.no_cfg5, a.two_stream) == (False, True, True, True, False)
+    assert a.steps == 20 and a.warmup == 5 and a.dump_outputs is None
+    a = _parse(["--full", "--no-cfg5", "--two-stream"], monkeypatch)
+    assert (a.full, a.no_cpu_baseline, a.no_pcie, a.no_cfg5, a.two_stream) == (True, False, False, True, True)
+    with pytest.raises(SystemExit):
+        _parse(["--op", "batcher", "--dump-outputs", "x"], monkeypatch)
+
+
+def test_keep_outputs_types_shapes_and_sample(tmp_path, monkeypatch):
+    """Bytes are written as float32 and 4-byte integers as float64 in their own shape, 8-byte words as
+    their bytes; an array over its share of the budget is cut to a sample that is the same in every
+    run, and the files together stay under 64 MB (here: under a budget of 4 000 bytes)."""
+    import argparse
+
+    import numpy as np
+    assert bench.DUMP_BYTES + 64 * 1024 <= 64 * 10**6           # room for the .npy headers
+    monkeypatch.setattr(bench, "DUMP_BYTES", 4000)
+    monkeypatch.setattr(bench, "DUMPED", {})
+    args = argparse.Namespace(dump_outputs=str(tmp_path / "d"))
+    rng = np.random.default_rng(1)
+    dig = rng.integers(0, 256, (10, 16), dtype=np.uint8)
+    lens = rng.integers(-2**31, 2**31, 25, dtype=np.int32)
+    words = rng.integers(0, 2**64, 5, dtype=np.uint64)
+    big = rng.integers(0, 256, 5000, dtype=np.uint8)
+    bench.keep_outputs(args, 0, 1, digests=dig, lens=lens, words=words, big=big)
+    first = {k: v.copy() for k, v in bench.DUMPED.items()}
+    bench.keep_outputs(args, 0, 1, digests=dig, lens=lens, words=words, big=big)
+    bench.write_outputs(args)
+    got = {f[:-4]: np.load(tmp_path / "d" / f) for f in sorted(os.listdir(tmp_path / "d"))}
+    assert sorted(got) == ["big", "digests", "lens", "words"]
+    assert all(np.array_equal(got[k], first[k]) for k in got)
+    assert got["digests"].dtype == np.float32 and np.array_equal(got["digests"], dig)
+    assert got["lens"].dtype == np.float64 and np.array_equal(got["lens"], lens)
+    assert got["words"].dtype == np.float32 and got["words"].astype(np.uint8).tobytes() == words.tobytes()
+    assert got["big"].dtype == np.float32 and got["big"].shape == (250,) and set(got["big"]) <= set(big.astype(float))
+    assert sum(a.nbytes for a in got.values()) <= 4000
+    # nothing is kept or written without the option
+    monkeypatch.setattr(bench, "DUMPED", {})
+    bench.keep_outputs(argparse.Namespace(dump_outputs=None), 0, 1, digests=dig)
+    assert bench.DUMPED == {}
+
+
+@pytest.mark.gpu
+def test_plain_headline_run_times_k_steps_and_dumps_digests(tmp_path):
+    """The plain headline run on a small batch: exactly K timed steps, none of the --full legs on the
+    line, and the dumped digests are the records' MD5 (hashlib)."""
+    import hashlib
+
+    import numpy as np
+    from brb_framework_amd import workload
+    n, L = 4099, 1500
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2",
+                          "--settle-s", "0", "--records-per-gpu", str(n), "--dump-outputs", str(tmp_path)],
+                         capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert FIELDS <= set(d) and d["steps"] == 7 and d["warmup"] == 2 and d["ms_per_step"] > 0
+    assert d["unit"] == "GiB/s" and d["dtype"] == "u32" and d["metric"] == bench.METRIC
+    assert not {"cfg5", "cpu_baseline", "pcie_inclusive", "two_stream_throughput"} & set(d)
+    got = np.load(tmp_path / "digests.npy")
+    assert got.dtype == np.float32 and got.shape == (n, 16)
+    host = workload.gen_records(workload.SEEDS[2], 0, n, L)
+    want = np.frombuffer(b"".join(hashlib.md5(host[i * L:(i + 1) * L].tobytes()).digest() for i in range(n)), np.uint8)
+    assert np.array_equal(got.astype(np.uint8).reshape(-1), want)
 
 
 class _Clock:

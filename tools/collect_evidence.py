@@ -3,7 +3,7 @@
 inside the line's timed region, and the line's roofline fraction recomputed from it.
 
 tools/gpu_evidence.sh runs each bench line as
-    rocprofv3 --kernel-trace --stats -d <dir>/<line> -o run -- python3 bench.py <args> --mark-timed-region
+    rocprofv3 --kernel-trace --stats -d <dir>/<line> -o run -- python3 bench.py --full <args> --mark-timed-region
 bench.py then enqueues one tiny `at::cuda::spin_kernel` right before and one right after each timed
 region (outside its timing), so the dispatches of a region are the ones that start after the first
 sentinel ends and end before the second one starts -- whatever ran before (warm-up, other legs)

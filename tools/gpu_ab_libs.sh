@@ -14,7 +14,7 @@ for r in $(seq 1 $R); do
   for v in gpurun_tmp_libs/*.so; do
     n=$(basename $v .so)
     cp $v brb_framework_amd/libbrb_crypto_gpu.so
-    timeout -k 10 200 python3 bench.py "$@" --no-cpu-baseline --no-pcie --no-cfg5 > $O/$n-$r.json 2> $O/$n-$r.err || { tail -3 $O/$n-$r.err; rc=1; break 2; }
+    timeout -k 10 200 python3 bench.py "$@" --full --no-cpu-baseline --no-pcie --no-cfg5 > $O/$n-$r.json 2> $O/$n-$r.err || { tail -3 $O/$n-$r.err; rc=1; break 2; }
     python3 -c "import json; d=json.load(open('$O/$n-$r.json')); print('$n', $r, d['value'], d['unit'], d['roofline'].get('launch_us_avg', d['roofline'].get('step_us_avg')))"
   done
 done

@@ -9,7 +9,7 @@ O=gpurun_out/${1:-abop}; PAT=$2; OPT=$3; VALS=$4; shift 4
 mkdir -p $O
 for x in $VALS; do
   n=$OPT-$x
-  timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $O/$n -o run -- python3 bench.py "$@" --test-option $OPT=$x --no-cpu-baseline --no-pcie --no-cfg5 > $O/$n.json 2> $O/$n.err || { echo "$n: bench failed"; tail -2 $O/$n.err; exit 1; }
+  timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $O/$n -o run -- python3 bench.py "$@" --test-option $OPT=$x --full --no-cpu-baseline --no-pcie --no-cfg5 > $O/$n.json 2> $O/$n.err || { echo "$n: bench failed"; tail -2 $O/$n.err; exit 1; }
   python3 -c "
 import csv
 for r in csv.DictReader(open('$O/$n/run_kernel_stats.csv')):

@@ -12,7 +12,7 @@ rc=0
 for v in gpurun_tmp_libs/*.so; do
   n=$(basename $v .so)
   cp $v brb_framework_amd/libbrb_crypto_gpu.so
-  timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $O/$n -o run -- python3 bench.py "$@" --no-cpu-baseline --no-pcie --no-cfg5 > $O/$n.json 2> $O/$n.err || { echo "$n: bench failed (stats still printed)"; tail -2 $O/$n.err; rc=1; }
+  timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $O/$n -o run -- python3 bench.py "$@" --full --no-cpu-baseline --no-pcie --no-cfg5 > $O/$n.json 2> $O/$n.err || { echo "$n: bench failed (stats still printed)"; tail -2 $O/$n.err; rc=1; }
   [ -f $O/$n/run_kernel_stats.csv ] && python3 -c "
 import csv
 for r in csv.DictReader(open('$O/$n/run_kernel_stats.csv')):

@@ -20,11 +20,11 @@ declare -A ARGS=(
 LINES=${@:-cfg2 sha1 cfg3 cfg4 rc4 rc4md5 metadata md5seg base64 md5var sha1var}
 for l in $LINES; do
   timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/$l" -o run -- \
-      python3 bench.py ${ARGS[$l]} --mark-timed-region > "$O/$l.json" 2> "$O/$l.err" \
+      python3 bench.py --full ${ARGS[$l]} --mark-timed-region > "$O/$l.json" 2> "$O/$l.err" \
       || { echo "$l failed"; tail -5 "$O/$l.err"; exit 1; }
   echo "$l ok"
 done
-timeout -k 10 300 python3 bench.py --config 1 > "$O/cfg1.json" 2> "$O/cfg1.err" && echo "cfg1 ok"
+timeout -k 10 300 python3 bench.py --full --config 1 > "$O/cfg1.json" 2> "$O/cfg1.err" && echo "cfg1 ok"
 timeout -k 10 300 python3 tools/collect_evidence.py "$O" "$O/evidence" $PLAIN || exit 1
 # the raw traces (tens of MB per line) stay on the box; the per-region summaries come back
 find "$O" -name run_kernel_trace.csv -delete

@@ -16,5 +16,5 @@ grep -E "PASSED|FAILED|Error" $O/old_lib.log | head -20
 cp $O/new.so brb_framework_amd/libbrb_crypto_gpu.so
 timeout -k 10 900 python -u -m pytest -x -v --timeout 120 --timeout-method thread tests -m gpu > $O/gpu_tests.log 2>&1
 rc=$?; tail -3 $O/gpu_tests.log; [ $rc -eq 0 ] || exit $rc
-timeout -k 10 300 python bench.py > $O/bench.json 2> $O/bench.err || { tail -5 $O/bench.err; exit 1; }
+timeout -k 10 300 python bench.py --full > $O/bench.json 2> $O/bench.err || { tail -5 $O/bench.err; exit 1; }
 cat $O/bench.json

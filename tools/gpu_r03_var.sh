@@ -13,7 +13,7 @@ for r in 1 2; do
   for n in 65536 524288; do
     for op in md5var sha1var; do
       for v in 1 0; do
-        timeout -k 10 200 python3 bench.py --op $op --records-per-gpu $n --no-cpu-baseline --test-option var_sort=$v > $O/$op-$n-$v-$r.json 2> $O/$op-$n-$v-$r.err || { tail -3 $O/$op-$n-$v-$r.err; exit 1; }
+        timeout -k 10 200 python3 bench.py --op $op --records-per-gpu $n --full --no-cpu-baseline --test-option var_sort=$v > $O/$op-$n-$v-$r.json 2> $O/$op-$n-$v-$r.err || { tail -3 $O/$op-$n-$v-$r.err; exit 1; }
         python3 -c "import json; d=json.load(open('$O/$op-$n-$v-$r.json')); print('$op n=$n var_sort=$v', $r, d['value'], d['roofline']['launch_us_avg'], d['roofline']['frac'])"
       done
     done

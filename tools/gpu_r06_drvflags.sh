@@ -6,7 +6,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out/r06drv2
 for i in 1 2 3; do
   for v in cfg5 nocfg5; do
-    extra=""; [ $v = nocfg5 ] && extra="--no-cfg5"
+    extra="--full"; [ $v = nocfg5 ] && extra="--full --no-cfg5"
     timeout -k 10 200 python bench.py --steps 20 --warmup 5 $extra > gpurun_out/r06drv2/$v-$i.json 2> gpurun_out/r06drv2/$v-$i.err || exit 1
     python3 -c "
 import json; d=json.load(open('gpurun_out/r06drv2/$v-$i.json')); print('$v', $i, d['value'], d['roofline']['launch_us_avg'], d['roofline']['frac'])

@@ -15,7 +15,7 @@ timeout -k 10 300 tools/mb/line_ab 1048576 1500 ${ROUNDS:-5} 40 > $O/line_ab_cfg
 grep -E "^n=|MEDIAN" $O/line_ab_cfg5.txt
 timeout -k 10 200 tools/mb/line_ab 65536 1500 ${ROUNDS:-5} 400 > $O/line_ab_cfg2.txt 2>&1 || { tail -5 $O/line_ab_cfg2.txt; exit 1; }
 grep -E "^n=|MEDIAN" $O/line_ab_cfg2.txt
-timeout -k 10 200 python3 bench.py --records-per-gpu 1048576 --no-cpu-baseline --no-pcie --no-cfg5 > $O/cfg5.json 2> $O/cfg5.err || { tail -3 $O/cfg5.err; exit 1; }
+timeout -k 10 200 python3 bench.py --records-per-gpu 1048576 --full --no-cpu-baseline --no-pcie --no-cfg5 > $O/cfg5.json 2> $O/cfg5.err || { tail -3 $O/cfg5.err; exit 1; }
 python3 -c "import json; d=json.load(open('$O/cfg5.json')); r=d['roofline']; print('bench cfg5 shard', round(r['launch_us_avg'],2), r['frac'])"
-timeout -k 10 200 python3 bench.py --no-cpu-baseline --no-pcie > $O/cfg2.json 2> $O/cfg2.err || { tail -3 $O/cfg2.err; exit 1; }
+timeout -k 10 200 python3 bench.py --full --no-cpu-baseline --no-pcie > $O/cfg2.json 2> $O/cfg2.err || { tail -3 $O/cfg2.err; exit 1; }
 python3 -c "import json; d=json.load(open('$O/cfg2.json')); r=d['roofline']; print('bench cfg2', round(r['launch_us_avg'],2), r['frac'], 'cfg5', d.get('cfg5'))"

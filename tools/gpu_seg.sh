@@ -13,13 +13,13 @@ tail -2 "$OUT/pytest.log"
 for r in 1 2; do
   for op in $OPS; do
     for v in 1 0; do
-      timeout -k 10 120 python bench.py --op $op --no-cpu-baseline --test-option seg_line=$v > "$OUT/b_${op}_${v}_$r.json" 2> "$OUT/b_${op}_${v}_$r.err" || { echo "bench $op $v failed"; tail -5 "$OUT/b_${op}_${v}_$r.err"; exit 1; }
+      timeout -k 10 120 python bench.py --op $op --full --no-cpu-baseline --test-option seg_line=$v > "$OUT/b_${op}_${v}_$r.json" 2> "$OUT/b_${op}_${v}_$r.err" || { echo "bench $op $v failed"; tail -5 "$OUT/b_${op}_${v}_$r.err"; exit 1; }
       python -c "import json,sys; d=json.load(open('$OUT/b_${op}_${v}_$r.json')); print('$op seg_line=$v', d['roofline']['launch_us_avg'], 'us', d['roofline']['frac'])"
     done
   done
 done
 for op in $OPS; do
 timeout -k 10 180 rocprofv3 --kernel-trace --stats -d "$OUT/prof_$op" -o run --output-format csv -- \
-    python3 bench.py --op $op --no-cpu-baseline > "$OUT/prof_$op.json" 2> "$OUT/prof_$op.err" || { echo "rocprof failed"; exit 1; }
+    python3 bench.py --op $op --full --no-cpu-baseline > "$OUT/prof_$op.json" 2> "$OUT/prof_$op.err" || { echo "rocprof failed"; exit 1; }
 done
 echo done

@@ -9,7 +9,7 @@ mkdir -p "$OUT"
 for a in "--config 2" "--op sha1 --no-cfg5" "--config 3" "--config 4" "--op rc4" "--op rc4md5" "--op metadata" \
          "--op md5seg" "--op base64" "--op md5var" "--op sha1var"; do
     n=$(echo "$a" | tr -d ' -')
-    timeout -k 10 300 python bench.py $a --steps 20 --warmup 5 --no-cpu-baseline --no-pcie > "$OUT/$n.json" 2> "$OUT/$n.err" \
+    timeout -k 10 300 python bench.py --full $a --steps 20 --warmup 5 --no-cpu-baseline --no-pcie > "$OUT/$n.json" 2> "$OUT/$n.err" \
         || { echo "$n failed"; tail -5 "$OUT/$n.err"; exit 1; }
     python3 -c "
 import json,sys;d=json.loads(open('$OUT/$n.json').read().strip().splitlines()[-1]);r=d.get('roofline') or {}

@@ -9,7 +9,7 @@ OUT=gpurun_out/${1:-short}
 mkdir -p "$OUT"
 run() {   # name, args...
     local n=$1; shift
-    timeout -k 10 240 python bench.py --no-pcie --no-cpu-baseline "$@" > "$OUT/$n.json" 2> "$OUT/$n.err" || return 1
+    timeout -k 10 240 python bench.py --full --no-pcie --no-cpu-baseline "$@" > "$OUT/$n.json" 2> "$OUT/$n.err" || return 1
     python3 - "$OUT/$n.json" "$n" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
