@@ -90,6 +90,9 @@ _SIGNATURES = [
     ("BRB_MetaDataUnpackBatch", ctypes.c_int,
      [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint,
       ctypes.c_void_p]),
+    ("BRB_MetaDataPackBatch", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+      ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint, ctypes.c_void_p]),
     ("BrbSha1_BatchFixed", ctypes.c_int,
      [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint, ctypes.c_void_p]),
     ("BrbSha1_Batch", ctypes.c_int,
@@ -341,6 +344,23 @@ def metadata_unpack_batch(data, offsets, lengths, out=None, stream=None, async_=
     flags, h = _mode(data, stream, async_, all_devices)
     _check(lib().BRB_MetaDataUnpackBatch(_ptr(data), _ptr(offsets), _ptr(lengths), n, _ptr(out), flags, h),
            "BRB_MetaDataUnpackBatch")
+    return out
+
+
+def metadata_pack_batch(data, item_offsets, item_lengths, item_ids, item_sub_ids, pack_first_item, out, out_offsets,
+                        stream=None, async_=False, all_devices=False):
+    """BRB_MetaDataPackBatch: MetaDataPack (meta_data.c:104-140) of pack p = items pack_first_item[p] ..
+    pack_first_item[p + 1] - 1 (n + 1 entries), item k = data[item_offsets[k] .. + item_lengths[k]) with
+    item_ids[k], item_sub_ids[k], written at out[out_offsets[p]:].  numpy arrays in host mode, CUDA
+    tensors in device mode (all nine the same kind); returns out."""
+    _same_kind(data, item_offsets, item_lengths, item_ids, item_sub_ids, pack_first_item, out, out_offsets)
+    n = len(pack_first_item) - 1
+    if n < 0 or len(out_offsets) < n:
+        raise ValueError("pack_first_item needs n + 1 entries and out_offsets n")
+    flags, h = _mode(data, stream, async_, all_devices)
+    _check(lib().BRB_MetaDataPackBatch(_ptr(data), _ptr(item_offsets), _ptr(item_lengths), _ptr(item_ids),
+                                       _ptr(item_sub_ids), _ptr(pack_first_item), n, _ptr(out), _ptr(out_offsets),
+                                       flags, h), "BRB_MetaDataPackBatch")
     return out
 
 

@@ -797,6 +797,94 @@ int metadata_unpack(const void *data, const uint64_t *offs, const uint32_t *lens
     return rc;
 }
 
+// MetaDataPack of n packs (metadata_pack_kernels.hip).  Host mode validates the item lists, stages the
+// span of the items and -- in both directions, so the bytes between packs survive -- the span of the
+// packs, as b64_batch stages its outputs.
+int metadata_pack(const void *data, const uint64_t *ioff, const uint32_t *ilen, const uint64_t *iid, const uint64_t *isub,
+                  const uint64_t *first, uint64_t n, void *out, const uint64_t *ooff, unsigned flags, void *stream)
+{
+    t_err.clear();
+    if (n == 0)
+        return BRB_BATCH_OK;
+    if (!data || !ioff || !ilen || !iid || !isub || !first || !out || !ooff) {
+        set_err("NULL data, item_offsets, item_lengths, item_ids, item_sub_ids, pack_first_item, out or out_offsets");
+        return BRB_BATCH_BADARG;
+    }
+    if (!items_ok(n) || !flags_ok(flags))
+        return BRB_BATCH_BADARG;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    hipError_t e;
+    if (flags & BRB_BATCH_DEVICE) {
+        if (int ok = device_ok(); ok != BRB_BATCH_OK)
+            return ok;
+        if ((e = brb::launch_metadata_pack(static_cast<const uint8_t *>(data), ioff, ilen, iid, isub, first, n,
+                                           static_cast<uint8_t *>(out), ooff, s)) != hipSuccess)
+            return fail_hip("kernel launch", e);
+        return finish(s, flags);
+    }
+    // host mode: the item lists are host memory, so they are checked before anything runs
+    std::vector<uint32_t> plen(n);              // pack sizes (a pack the unpack call can take: a uint32 length)
+    for (uint64_t p = 0; p < n; p++) {
+        if (first[p + 1] < first[p]) {
+            set_err("pack_first_item is not non-decreasing at %llu", (unsigned long long)p);
+            return BRB_BATCH_BADARG;
+        }
+        if (first[p + 1] - first[p] > uint64_t(INT32_MAX)) {
+            set_err("pack %llu: %llu items (the header's item count is an int)", (unsigned long long)p,
+                    (unsigned long long)(first[p + 1] - first[p]));
+            return BRB_BATCH_BADARG;
+        }
+        uint64_t size = BRB_METADATA_HEADER_SIZE;
+        for (uint64_t k = first[p]; k < first[p + 1]; k++)
+            size += uint64_t(ilen[k]) + BRB_METADATA_ITEM_RAW_SIZE + 1;
+        if (size > UINT32_MAX) {
+            set_err("pack %llu: %llu bytes (host mode packs at most 4 GiB - 1, the unpack call's length)",
+                    (unsigned long long)p, (unsigned long long)size);
+            return BRB_BATCH_BADARG;
+        }
+        plen[p] = uint32_t(size);
+    }
+    if (int ok = device_ok(); ok != BRB_BATCH_OK)
+        return ok;
+    if (flags & BRB_BATCH_ALL_DEVICES) {   // packs are written back: their spans must not interleave
+        flags &= ~BRB_BATCH_ALL_DEVICES;
+        if (parts_disjoint(ooff, plen.data(), n, 0))
+            return brb_host::split_devices(n, [&](int, uint64_t lo, uint64_t hi) {
+                return metadata_pack(data, ioff, ilen, iid, isub, first + lo, hi - lo, out, ooff + lo, flags, nullptr);
+            });
+    }
+    const uint64_t k0 = first[0], nitem = first[n] - k0;
+    uint64_t lo, hi, olo, ohi;
+    if (!span_of(ioff + k0, ilen + k0, nitem, 0, lo, hi) || !span_of(ooff, plen.data(), n, 0, olo, ohi))
+        return BRB_BATCH_BADARG;
+    const std::vector<uint64_t> roff = rebase(ioff + k0, nitem, lo), rooff = rebase(ooff, n, olo);
+    std::vector<uint64_t> rfirst(first, first + n + 1);
+    for (uint64_t &f : rfirst)
+        f -= k0;
+    Staging st;
+    const size_t i_d = st.add(static_cast<const uint8_t *>(data) + lo, nullptr, size_t(hi - lo));
+    const size_t i_out = st.add(static_cast<uint8_t *>(out) + olo, static_cast<uint8_t *>(out) + olo, size_t(ohi - olo));
+    const size_t i_o = st.add(roff.data(), nullptr, 8 * nitem);
+    const size_t i_l = st.add(ilen + k0, nullptr, 4 * nitem);
+    const size_t i_id = st.add(iid + k0, nullptr, 8 * nitem);
+    const size_t i_sub = st.add(isub + k0, nullptr, 8 * nitem);
+    const size_t i_f = st.add(rfirst.data(), nullptr, 8 * (n + 1));
+    const size_t i_oo = st.add(rooff.data(), nullptr, 8 * n);
+    int rc = st.upload(s);
+    if (rc == BRB_BATCH_OK &&
+        (e = brb::launch_metadata_pack(st.dev(i_d), reinterpret_cast<const uint64_t *>(st.dev(i_o)),
+                                       reinterpret_cast<const uint32_t *>(st.dev(i_l)),
+                                       reinterpret_cast<const uint64_t *>(st.dev(i_id)),
+                                       reinterpret_cast<const uint64_t *>(st.dev(i_sub)),
+                                       reinterpret_cast<const uint64_t *>(st.dev(i_f)), n, st.dev(i_out),
+                                       reinterpret_cast<const uint64_t *>(st.dev(i_oo)), s)) != hipSuccess)
+        rc = fail_hip("kernel launch", e);
+    if (rc == BRB_BATCH_OK)
+        return st.download(s);
+    (void)hipStreamSynchronize(s);
+    return rc;
+}
+
 // ---- base64 --------------------------------------------------------------------
 int b64_batch(bool decode, const void *in, const uint64_t *offs, const uint32_t *lens, uint64_t n, void *out,
               const uint64_t *ooffs, uint32_t *olens, unsigned flags, void *stream)
@@ -992,6 +1080,14 @@ int BRB_MetaDataUnpackBatch(const void *data, const uint64_t *offsets, const uin
                             BRB_MetaDataUnpackInfo *info, unsigned flags, void *hip_stream)
 {
     return metadata_unpack(data, offsets, lengths, n_packs, info, flags, hip_stream);
+}
+
+int BRB_MetaDataPackBatch(const void *data, const uint64_t *item_offsets, const uint32_t *item_lengths,
+                          const uint64_t *item_ids, const uint64_t *item_sub_ids, const uint64_t *pack_first_item,
+                          uint64_t n_packs, void *out, const uint64_t *out_offsets, unsigned flags, void *hip_stream)
+{
+    return metadata_pack(data, item_offsets, item_lengths, item_ids, item_sub_ids, pack_first_item, n_packs, out,
+                         out_offsets, flags, hip_stream);
 }
 
 int BrbSha1_BatchFixed(const void *data, uint32_t rec_len, uint64_t n_rec, uint8_t (*digests)[20], unsigned flags,

@@ -30,6 +30,12 @@ hipError_t launch_md5_segments(const uint8_t *data, const uint64_t *soff, const 
 hipError_t launch_metadata_unpack(const uint8_t *data, const uint64_t *offs, const uint32_t *lens, uint64_t n,
                                   BRB_MetaDataUnpackInfo *info, hipStream_t s);
 
+// MetaDataPack of whole packs (metadata_pack_kernels.hip): pack p = items first[p] .. first[p + 1] - 1, item k =
+// data[ioff[k] .. + ilen[k]) with iid[k], isub[k]; written at out + ooff[p]
+hipError_t launch_metadata_pack(const uint8_t *data, const uint64_t *ioff, const uint32_t *ilen, const uint64_t *iid,
+                                const uint64_t *isub, const uint64_t *first, uint64_t n_packs, uint8_t *out,
+                                const uint64_t *ooff, hipStream_t s);
+
 // base64 (base64_kernels.hip)
 hipError_t launch_b64_encode(const uint8_t *in, const uint64_t *offs, const uint32_t *lens, uint64_t n, uint8_t *out,
                              const uint64_t *ooffs, uint64_t mean_len, hipStream_t s);

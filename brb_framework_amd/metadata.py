@@ -7,8 +7,13 @@ A pack is a 64-byte header {int version = 0; int item_count; unsigned long size;
 of the items' data (MetaDataHeaderLoadData, :397-433); 24 zero bytes}, then per item
 {unsigned long item_id, item_sub_id, sz; sz data bytes; 0x1F}; size = sum of (sz + 24 + 1).
 
-pack_batch lays packs out back to back on the host and computes every header digest with one
-BRB_MD5BatchSegments call whose segments are the item data inside the packed buffer itself;
+pack_items_batch builds the packs on the GPU: it gathers the items' bytes and the item lists into
+numpy arrays and makes one BRB_MetaDataPackBatch call (one GPU lane per pack, every item byte read
+once for both the digest and the pack; crypto.metadata_pack_batch is the call itself, for callers
+whose items already lie in one buffer, on the host or in HBM).  pack_sizes gives the packs' lengths
+from the item lists.  pack_batch is the earlier host-side builder: it lays packs out back to back on
+the host and computes every header digest with one BRB_MD5BatchSegments call whose segments are the
+item data inside the packed buffer itself.
 unpack_batch is BRB_MetaDataUnpackBatch (one GPU lane per pack; reference return codes and
 MetaDataUnpackerInfo fields, quirks included -- include/brb_crypto.h).  items() lists a pack's items
 on the host, for packs unpack_batch accepted."""
@@ -34,7 +39,9 @@ def pack_size(items) -> int:
 
 def pack_batch(packs):
     """MetaDataPack of every MetaData in `packs` (each a list of (item_id, item_sub_id, data bytes)).
-    Returns (buf, offsets, lengths): pack i is buf[offsets[i] : offsets[i] + lengths[i]]."""
+    Returns (buf, offsets, lengths): pack i is buf[offsets[i] : offsets[i] + lengths[i]].
+    Built on the host, digests by BRB_MD5BatchSegments; pack_items_batch returns the same triple from
+    one BRB_MetaDataPackBatch call."""
     sizes = np.array([pack_size(items) for items in packs], np.uint64)
     offsets = np.zeros(len(packs), np.uint64)
     if len(packs) > 1:
@@ -62,6 +69,39 @@ def pack_batch(packs):
         for p in range(len(packs)):
             o = int(offsets[p]) + 24
             buf[o:o + 16] = digests[p]
+    return buf, offsets, sizes.astype(np.uint32)
+
+
+def pack_sizes(item_lengths, pack_first_item):
+    """Bytes of every pack BRB_MetaDataPackBatch writes: HEADER + sum(item length + 25) over items
+    pack_first_item[p] .. pack_first_item[p + 1] - 1 (uint64[n])."""
+    first = np.asarray(pack_first_item, np.uint64).astype(np.int64)
+    cum = np.zeros(len(item_lengths) + 1, np.uint64)
+    np.cumsum(np.asarray(item_lengths, np.uint64) + np.uint64(ITEM_RAW + 1), out=cum[1:])
+    return cum[first[1:]] - cum[first[:-1]] + np.uint64(HEADER)
+
+
+def pack_items_batch(packs, stream=None, all_devices=False):
+    """MetaDataPack of every MetaData in `packs` (each a list of (item_id, item_sub_id, data bytes)) by
+    one BRB_MetaDataPackBatch call.  Returns (buf, offsets, lengths) as pack_batch does: pack i is
+    buf[offsets[i] : offsets[i] + lengths[i]], the packs back to back."""
+    items = [it for p in packs for it in p]
+    lens = np.fromiter((len(d) for _, _, d in items), np.uint32, len(items))
+    ids = np.array([i for i, _, _ in items], np.uint64)
+    subs = np.array([s for _, s, _ in items], np.uint64)
+    first = np.zeros(len(packs) + 1, np.uint64)
+    np.cumsum(np.fromiter((len(p) for p in packs), np.uint64, len(packs)), out=first[1:])
+    item_off = np.zeros(len(items), np.uint64)
+    if len(items) > 1:
+        item_off[1:] = np.cumsum(lens[:-1], dtype=np.uint64)
+    data = np.frombuffer(b"".join(d for _, _, d in items) + b"\0", np.uint8)
+    sizes = pack_sizes(lens, first)
+    offsets = np.zeros(len(packs), np.uint64)
+    if len(packs) > 1:
+        offsets[1:] = np.cumsum(sizes)[:-1]
+    buf = np.zeros(int(sizes.sum()) if len(packs) else 1, np.uint8)
+    crypto.metadata_pack_batch(data, item_off, lens, ids, subs, first, buf, offsets, stream=stream,
+                               all_devices=all_devices)
     return buf, offsets, sizes.astype(np.uint32)
 
 

@@ -136,7 +136,7 @@ void BRB_RC4_Crypt(BRB_RC4_State *state, const unsigned char *inbuf, unsigned ch
                                       ranges [g*n/G, (g+1)*n/G), one per visible device g < G, run
                                       them concurrently and return when all are done (SURVEY §8(e):
                                       no collective); the RC4 states go with their streams.  Calls
-                                      that write a byte span back (RC4, frames, base64 outputs)
+                                      that write a byte span back (RC4, frames, base64 outputs, MetaData packs)
                                       split only when the ranges' spans do not interleave across
                                       parts (ranges in submission order); otherwise they run on the
                                       calling thread's device.  With BRB_BATCH_DEVICE: -1.           */
@@ -202,6 +202,28 @@ typedef struct BRB_MetaDataUnpackInfo {
 } BRB_MetaDataUnpackInfo;
 int BRB_MetaDataUnpackBatch(const void *data, const uint64_t *offsets, const uint32_t *lengths, uint64_t n_packs,
                             BRB_MetaDataUnpackInfo *info, unsigned flags, void *hip_stream);
+
+/* MetaDataPack (meta_data.c:104-140, digest :397-433) for n_packs MetaDatas.  Pack p holds items
+ * pack_first_item[p] .. pack_first_item[p+1]-1 (n_packs + 1 entries, non-decreasing); item k =
+ * data[item_offsets[k] .. + item_lengths[k]) with item_ids[k], item_sub_ids[k].  Pack p is written
+ * at out + out_offsets[p] and is BRB_METADATA_HEADER_SIZE + sum(item_lengths[k] + 25) bytes long:
+ * the header above (version 0, (int) item count, size = sum(item_lengths[k] + 25), "BRB_META", the
+ * MD5 of the items' data in order -- BRB_MD5Init, one BRB_MD5UpdateBig per item, BRB_MD5Final -- and
+ * 24 zero bytes), then per item its three unsigned longs, its data and the 0x1F canary.  A pack with
+ * no items is the header alone, with the MD5 of the empty message; the address of a zero-length item
+ * is never read.  Exactly the pack's bytes are written: packs may lie back to back at any byte
+ * offset of out, and bytes between packs keep their values.  Packs must not overlap each other or
+ * the items they (or other packs of the call) are built from.  A pack holds at most INT32_MAX
+ * items, and in host mode at most 4 GiB - 1 bytes, the unpack call's length (host mode: -1
+ * otherwise; pack_first_item that decreases: -1; device mode validates nothing).  Host mode stages the span
+ * of out that the packs cover in both directions.  BRB_BATCH_ALL_DEVICES splits the packs into
+ * contiguous ranges only when those ranges' output spans do not interleave (as the RC4 and base64
+ * calls); otherwise the call runs on the calling thread's device.  One pass on the GPU: every item
+ * byte is read from HBM once and feeds both the digest and the pack. */
+int BRB_MetaDataPackBatch(const void *data, const uint64_t *item_offsets, const uint32_t *item_lengths,
+                          const uint64_t *item_ids, const uint64_t *item_sub_ids,
+                          const uint64_t *pack_first_item, uint64_t n_packs,
+                          void *out, const uint64_t *out_offsets, unsigned flags, void *hip_stream);
 
 /* SHA-1 batches: digests[i] = BrbSha1_Do(record i) (20 raw big-endian bytes).  Unlike
  * BrbSha1_Update the batch surface never writes into the input records. */
