@@ -16,7 +16,7 @@ enum Opt {
                         // k > 0: they split into k parts, part g on device g % (visible devices) --
                         // the concurrent multi-device paths exercised on a one-GPU box
     kB64Group = 5,      // -1: the launcher's choice; 0..6: log2 of the base64 lanes per record
-    kHostChunkMiB = 6,  // 0: host-mode Blowfish/RC4 chunks of 16 MiB; k: k MiB (tools/host_sweep.py)
+    kHostChunkMiB = 6,  // 0: host-mode Blowfish chunks of 16 MiB; k: k MiB (RC4 host mode is not chunked)
     kHostDigestChunkMiB = 7,   // 0: host-mode digest chunks of 32 MiB; k: k MiB
     kSegLine = 8,       // segment digests / MetaData unpack: 2 line-staged wave pairs (default), 1 line-staged
                         // single waves, 0 the per-lane kernels

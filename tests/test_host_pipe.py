@@ -1,11 +1,12 @@
 """Host-mode batches (host_pipe.hip) and the multi-device runtime, against the oracle.
 
-Host mode copies straight from the caller's memory in 16 MiB chunks, overlapping the H2D copy of one
-chunk with the kernel on the previous one and (Blowfish) the D2H copy of an earlier one.  These tests
-cut batches so that chunk boundaries fall inside records and the last chunk is short, with pageable
-(numpy) and page-locked (torch pin_memory) buffers, and run the BRB_BATCH_ALL_DEVICES split (contiguous
-record ranges over every visible device; one range on a one-GPU box).  Every result is compared
-with the oracle bit for bit.
+Host mode copies straight from the caller's memory in chunks (32 MiB for digests, 16 MiB for
+Blowfish; tests/test_batch_ends.py shrinks them to 1 MiB to reach the chunk edges), overlapping the
+H2D copy of one chunk with the kernel on the previous one and the D2H copy of an earlier one.  These
+tests cut batches so that chunk boundaries fall inside records and the last chunk is short, with
+pageable (numpy) and page-locked (torch pin_memory) buffers, and run the BRB_BATCH_ALL_DEVICES split
+(contiguous record ranges over every visible device; one range on a one-GPU box).  Every result is
+compared with the oracle bit for bit.
 """
 import ctypes
 import threading
@@ -31,9 +32,9 @@ def pinned_copy(a):
 
 
 @pytest.mark.parametrize("n,rec_len", [
-    (30_000, 1500),      # 45 MB: three chunks, chunk edges at whole records (line-staged kernel)
+    (30_000, 1500),      # 45 MB: two 32 MiB digest chunks, the edge at a whole record (line-staged kernel)
     (23_456, 1501),      # record-relative kernel, ragged last chunk
-    (400_000, 64),       # 64-byte records: 25.6 MB, two chunks
+    (400_000, 64),       # 64-byte records: 25.6 MB, one chunk (chunk edges: test_batch_ends.py)
     (12, 3_000_000),     # 3 MB records: five per chunk
 ])
 def test_fixed_digests_chunked(gpu, orc, n, rec_len):
