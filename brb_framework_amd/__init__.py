@@ -59,6 +59,11 @@ from .crypto import (  # noqa: F401
     membuf_span,
     rc4_crypt_batch,
     rc4_init,
+    rc4_init_batch,
+    blowfish_init_batch,
+    pack_keys,
+    unpack_keys,
+    BLOWFISH_CTX_BYTES,
     rc4_state_bytes,
     rc4_states,
     rc4md5_frame_batch,
@@ -77,4 +82,5 @@ __all__ = [
     "base64_encode_batch", "CRYPTO_FUNC_RC4", "CRYPTO_FUNC_RC4_MD5", "OP_READ", "OP_WRITE", "TransformBatcher",
     "HostRegion", "BATCHER_ZERO_COPY", "BATCHER_PIPELINED", "BATCH_ALL_DEVICES", "device_count",
     "BATCH_DROPPED", "TRANSFORM_DROPPED", "BATCHER_ALL_DEVICES", "TestOption", "test_option", "async_fault_check",
+    "rc4_init_batch", "blowfish_init_batch", "pack_keys", "unpack_keys", "BLOWFISH_CTX_BYTES",
 ]

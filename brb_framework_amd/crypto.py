@@ -102,6 +102,14 @@ _SIGNATURES = [
      [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint, ctypes.c_void_p]),
     ("BRB_Blowfish_DecryptBatch", ctypes.c_int,
      [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint, ctypes.c_void_p]),
+    ("BRB_RC4_InitBatch", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint,
+      ctypes.c_void_p]),
+    ("BRB_Blowfish_InitBatch", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint,
+      ctypes.c_void_p]),
+    ("BRB_TransformBatcherEnableBatch", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     ("BRB_RC4_CryptBatch", ctypes.c_int,
      [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
       ctypes.c_uint, ctypes.c_void_p]),
@@ -440,6 +448,56 @@ def _same_kind(ref, *xs):
             raise ValueError("all buffers of one batch call must be numpy (host) or all CUDA tensors (device)")
 
 
+# ---- key setup as a batch (EvAIOReqTransform_CryptoEnable for many keys) ---------------------------
+BLOWFISH_CTX_BYTES = 8336
+
+
+def pack_keys(keys):
+    """A list of `bytes` keys -> (blob uint8[sum], key_offsets uint64[n], key_lengths uint32[n]), the keys
+    back to back in list order (so every offset residue mod 4 occurs with odd lengths)."""
+    lens = np.array([len(k) for k in keys], np.uint32)
+    offs = np.zeros(len(keys), np.uint64)
+    if len(keys) > 1:
+        offs[1:] = np.cumsum(lens[:-1], dtype=np.uint64)
+    blob = np.frombuffer(b"".join(bytes(k) for k in keys), np.uint8).copy()
+    return blob, offs, lens
+
+
+def unpack_keys(blob, key_offsets, key_lengths):
+    """The inverse of pack_keys for any layout (shared or overlapping keys included): a list of bytes."""
+    raw = np.asarray(blob, np.uint8).tobytes()
+    return [raw[int(o):int(o) + int(n)] for o, n in zip(key_offsets, key_lengths)]
+
+
+def _init_batch(fn, width, keys, key_offsets, key_lengths, out, stream, async_, all_devices):
+    _same_kind(keys, key_offsets, key_lengths, out)
+    n = len(key_offsets)
+    if len(key_lengths) != n:
+        raise ValueError("key_offsets and key_lengths differ in length")
+    if out is None:
+        out = _out_like(keys, n, width)
+    elif _nbytes(out) < n * width:
+        raise ValueError(f"out holds {_nbytes(out)} bytes, {n} records need {n * width}")
+    flags, h = _mode(keys, stream, async_, all_devices)
+    _check(fn(_ptr(out), _ptr(keys), _ptr(key_offsets), _ptr(key_lengths), n, flags, h), fn.__name__)
+    return out
+
+
+def rc4_init_batch(keys, key_offsets, key_lengths, out=None, stream=None, async_=False, all_devices=False):
+    """BRB_RC4_InitBatch: (n, 264) uint8 states, state i = zeroed + BRB_RC4_Init(keys[key_offsets[i]:
+    +key_lengths[i]]).  keys uint8, key_offsets uint64[n], key_lengths uint32[n] (pack_keys): numpy for
+    host mode, CUDA tensors for device mode (offsets int64, lengths int32)."""
+    return _init_batch(lib().BRB_RC4_InitBatch, RC4_STATE_BYTES, keys, key_offsets, key_lengths, out, stream, async_,
+                       all_devices)
+
+
+def blowfish_init_batch(keys, key_offsets, key_lengths, out=None, stream=None, async_=False, all_devices=False):
+    """BRB_Blowfish_InitBatch: (n, 8336) uint8 contexts, row i = BRB_Blowfish_Init of key i; a row of a
+    device-mode result is the `ctx` of blowfish_encrypt_batch / blowfish_decrypt_batch as it stands."""
+    return _init_batch(lib().BRB_Blowfish_InitBatch, BLOWFISH_CTX_BYTES, keys, key_offsets, key_lengths, out, stream,
+                       async_, all_devices)
+
+
 def rc4_crypt_batch(states, data, offsets, lengths, out=None, stream=None, async_=False, all_devices=False):
     """BRB_RC4_CryptBatch: stream i = data[offsets[i]:+lengths[i]] -> out (in place when out is None).
     states: (n, 264) uint8, updated in place."""
@@ -620,6 +678,18 @@ class TransformBatcher:
 
     def enable(self, conn: int, key: bytes):
         _check(self._L.BRB_TransformBatcherEnable(self.h, conn, bytes(key), len(key)), "BRB_TransformBatcherEnable")
+
+    def enable_batch(self, conns, keys):
+        """BRB_TransformBatcherEnableBatch: connection conns[i] gets keys[i] (bytes), read and write
+        state, in one GPU call."""
+        if len(conns) != len(keys):
+            raise ValueError("conns and keys differ in length")
+        ids = np.ascontiguousarray(conns, np.uint32)
+        blob, offs, lens = pack_keys(keys)
+        if blob.size == 0:
+            blob = np.zeros(1, np.uint8)
+        _check(self._L.BRB_TransformBatcherEnableBatch(self.h, _ptr(ids), len(ids), _ptr(blob), _ptr(offs), _ptr(lens)),
+               "BRB_TransformBatcherEnableBatch")
 
     def read(self, conn: int, data: bytes) -> int:
         if self._regions is not None:

@@ -748,6 +748,75 @@ int md5_segments(const void *data, const uint64_t *soff, const uint32_t *slen, c
     return rc;
 }
 
+// ---- key setup (EvAIOReqTransform_CryptoEnable for many keys; keysetup_kernels.hip) -----------
+// blowfish: BRB_Blowfish_InitBatch (8336-byte contexts, 72 key bytes used); else BRB_RC4_InitBatch
+// (264-byte states, 256 key bytes used).  Outputs are fixed-stride, so BRB_BATCH_ALL_DEVICES always
+// splits into contiguous ranges.  No wave-pair kernel: no fault word.
+int keysetup_batch(bool blowfish, void *out, const void *keys, const uint64_t *koffs, const uint32_t *klens, uint64_t n,
+                   unsigned flags, void *stream)
+{
+    t_err.clear();
+    if (n == 0)
+        return BRB_BATCH_OK;
+    if (!out || !keys || !koffs || !klens) {
+        set_err("NULL %s, keys, key_offsets or key_lengths", blowfish ? "ctxs" : "states");
+        return BRB_BATCH_BADARG;
+    }
+    if (!items_ok(n) || !flags_ok(flags))
+        return BRB_BATCH_BADARG;
+    const size_t stride = blowfish ? sizeof(BRB_BLOWFISH_CTX) : sizeof(BRB_RC4_State);
+    const uint32_t used_max = blowfish ? 72u : 256u;
+    std::vector<uint32_t> used;                 // host mode: the key bytes the schedule reads
+    if (!(flags & BRB_BATCH_DEVICE)) {
+        used.resize(n);
+        for (uint64_t i = 0; i < n; i++) {
+            if (klens[i] == 0) {
+                set_err("key %llu: zero length", (unsigned long long)i);
+                return BRB_BATCH_BADARG;
+            }
+            used[i] = std::min(klens[i], used_max);
+        }
+    }
+    if (int ok = device_ok(); ok != BRB_BATCH_OK)
+        return ok;
+    if (flags & BRB_BATCH_ALL_DEVICES)   // contiguous key ranges, one per device
+        return brb_host::split_devices(n, [&](int, uint64_t lo, uint64_t hi) {
+            return keysetup_batch(blowfish, static_cast<uint8_t *>(out) + lo * stride, keys, koffs + lo, klens + lo, hi - lo,
+                                  flags & ~BRB_BATCH_ALL_DEVICES, nullptr);
+        });
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    auto launch = [&](uint8_t *o, const uint8_t *k, const uint64_t *off, const uint32_t *len) {
+        return blowfish ? brb::launch_blowfish_keysetup(reinterpret_cast<uint64_t *>(o), k, off, len, n, s)
+                        : brb::launch_rc4_keysetup(o, k, off, len, n, s);
+    };
+    hipError_t e;
+    if (flags & BRB_BATCH_DEVICE) {
+        if ((e = launch(static_cast<uint8_t *>(out), static_cast<const uint8_t *>(keys), koffs, klens)) != hipSuccess)
+            return fail_hip("kernel launch", e);
+        return finish(s, flags);
+    }
+    // host mode: the span of the key bytes read, with the offsets rebased to it and the lengths clamped
+    // to the bytes used (the same schedule: RC4 indexes key[k % len] with k < 256, Blowfish takes 72 bytes)
+    uint64_t lo, hi;
+    if (!span_of(koffs, used.data(), n, 0, lo, hi))
+        return BRB_BATCH_BADARG;
+    const std::vector<uint64_t> roff = rebase(koffs, n, lo);
+    Staging st;
+    const size_t i_k = st.add(static_cast<const uint8_t *>(keys) + lo, nullptr, size_t(hi - lo));
+    const size_t i_o = st.add(roff.data(), nullptr, 8 * n);
+    const size_t i_l = st.add(used.data(), nullptr, 4 * n);
+    const size_t i_out = st.add(nullptr, out, stride * n);
+    int rc = st.upload(s);
+    if (rc == BRB_BATCH_OK &&
+        (e = launch(st.dev(i_out), st.dev(i_k), reinterpret_cast<const uint64_t *>(st.dev(i_o)),
+                    reinterpret_cast<const uint32_t *>(st.dev(i_l)))) != hipSuccess)
+        rc = fail_hip("kernel launch", e);
+    if (rc == BRB_BATCH_OK)
+        return st.download(s);
+    (void)hipStreamSynchronize(s);
+    return rc;
+}
+
 // ---- MetaData packs ------------------------------------------------------------
 int metadata_unpack(const void *data, const uint64_t *offs, const uint32_t *lens, uint64_t n,
                     BRB_MetaDataUnpackInfo *info, unsigned flags, void *stream)
@@ -1112,6 +1181,18 @@ int BRB_Blowfish_DecryptBatch(const BRB_BLOWFISH_CTX *ctx, unsigned long *words,
                               void *hip_stream)
 {
     return blowfish_batch(ctx, words, n_blocks, flags, hip_stream, true);
+}
+
+int BRB_RC4_InitBatch(BRB_RC4_State *states, const void *keys, const uint64_t *key_offsets, const uint32_t *key_lengths,
+                      uint64_t n_keys, unsigned flags, void *hip_stream)
+{
+    return keysetup_batch(false, states, keys, key_offsets, key_lengths, n_keys, flags, hip_stream);
+}
+
+int BRB_Blowfish_InitBatch(BRB_BLOWFISH_CTX *ctxs, const void *keys, const uint64_t *key_offsets,
+                           const uint32_t *key_lengths, uint64_t n_keys, unsigned flags, void *hip_stream)
+{
+    return keysetup_batch(true, ctxs, keys, key_offsets, key_lengths, n_keys, flags, hip_stream);
 }
 
 int BRB_RC4_CryptBatch(BRB_RC4_State *states, const void *in, void *out, const uint64_t *offsets, const uint32_t *lengths,

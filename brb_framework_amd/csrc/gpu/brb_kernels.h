@@ -57,4 +57,13 @@ hipError_t launch_rc4md5_open(uint8_t *states, const uint8_t *in, uint8_t *out, 
                               const uint32_t *lens, uint64_t n, uint8_t *valid, hipStream_t s,
                               const uint32_t *sidx = nullptr, const uint64_t *ooffs = nullptr);
 
+// Key setup (keysetup_kernels.hip): key i = keys[koffs[i] .. + klens[i]).
+// RC4: the zeroed-then-BRB_RC4_Init state of key i is written (all 264 bytes) to states[slots ? slots[i] : i],
+// and, when second != 0, also `second` bytes after it (the transform batcher's write-state table).
+hipError_t launch_rc4_keysetup(uint8_t *states, const uint8_t *keys, const uint64_t *koffs, const uint32_t *klens,
+                               uint64_t n, hipStream_t s, const uint32_t *slots = nullptr, uint64_t second = 0);
+// Blowfish: ctxs[i] (1042 qwords, 8-byte aligned) = BRB_Blowfish_Init of key i
+hipError_t launch_blowfish_keysetup(uint64_t *ctxs, const uint8_t *keys, const uint64_t *koffs, const uint32_t *klens,
+                                    uint64_t n, hipStream_t s);
+
 }  // namespace brb

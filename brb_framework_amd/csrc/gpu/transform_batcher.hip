@@ -289,6 +289,15 @@ struct BRB_TransformBatcher {
     }
 };
 
+// What a successful key setup leaves behind (Enable and EnableBatch): the connection takes buffers
+// again and starts its next key epoch, so buffers from here on belong to the fresh key and a
+// poisoned connection is re-keyed.
+static void key_installed(BRB_TransformBatcher *b, uint32_t conn)
+{
+    b->enabled[conn] = 1;
+    __atomic_fetch_add(&b->epoch[conn], 1u, __ATOMIC_RELEASE);   // buffers from here on: the fresh key
+}
+
 extern "C" {
 
 BRB_TransformBatcher *BRB_TransformBatcherCreate(uint32_t max_conns, uint64_t max_round_bytes, int algo)
@@ -404,8 +413,7 @@ int BRB_TransformBatcherEnable(BRB_TransformBatcher *b, uint32_t conn, const voi
             return fail_hip("hipMemcpyAsync H2D", e);
     if ((e = hipStreamSynchronize(b->stream)) != hipSuccess)
         return fail_hip("hipStreamSynchronize", e);
-    b->enabled[conn] = 1;
-    __atomic_fetch_add(&b->epoch[conn], 1u, __ATOMIC_RELEASE);   // buffers from here on: the fresh key
+    key_installed(b, conn);
     return BRB_BATCH_OK;
 }
 
@@ -494,6 +502,149 @@ int BRB_TransformBatcherWrite(BRB_TransformBatcher *b, uint32_t conn, const void
 }
 
 }  // extern "C"
+
+// ---- EnableBatch: EvAIOReqTransform_CryptoEnable for many connections ---------------------------
+// One part per batcher (an all-devices batcher: one per sub-batcher, connection c in part c % G as
+// its connection c / G).  enqueue() puts one H2D copy -- the span of the key bytes read, the rebased
+// offsets, the lengths and the connection slots, packed in one host buffer -- and one key-schedule
+// kernel on the part's stream; the kernel writes the read and the write state of every listed
+// connection into d_states.  finish() waits for the stream.  Every part is enqueued before any is
+// waited for.
+namespace {
+
+struct EnablePart {
+    BRB_TransformBatcher *b = nullptr;
+    std::vector<uint32_t> conns;       // the part's own connection ids
+    std::vector<uint64_t> which;       // index into the caller's arrays
+    std::vector<uint8_t> host;         // keys | offsets | lengths | slots (kept until the stream has drained)
+    uint8_t *dev = nullptr;
+    bool enqueued = false;
+    std::string err;
+
+    void fail(const char *what, hipError_t e)
+    {
+        fail_hip(what, e);
+        err = brb_api::t_err;
+    }
+
+    void enqueue(const uint8_t *keys, const uint64_t *koffs, const uint32_t *klens)
+    {
+        const size_t n = conns.size();
+        uint64_t lo = UINT64_MAX, hi = 0;
+        for (uint64_t i : which) {       // only the first 256 key bytes are read (rc4.c:53: key[k % keylen], k < 256)
+            lo = std::min(lo, koffs[i]);
+            hi = std::max(hi, koffs[i] + std::min<uint64_t>(klens[i], 256));
+        }
+        const size_t span = size_t(hi - lo), o_off = up(span, 8), o_len = o_off + 8 * n, o_slot = o_len + 4 * n;
+        host.resize(o_slot + 4 * n);
+        memcpy(host.data(), keys + lo, span);
+        uint64_t *off = reinterpret_cast<uint64_t *>(host.data() + o_off);
+        uint32_t *len = reinterpret_cast<uint32_t *>(host.data() + o_len);
+        uint32_t *slot = reinterpret_cast<uint32_t *>(host.data() + o_slot);
+        for (size_t k = 0; k < n; k++) {
+            off[k] = koffs[which[k]] - lo;
+            len[k] = klens[which[k]];
+            slot[k] = conns[k];
+        }
+        DeviceGuard g(b->dev);
+        hipError_t e;
+        if ((e = g.error()) != hipSuccess)
+            return fail("hipSetDevice", e);
+        void *p = nullptr;
+        if ((e = hipMalloc(&p, host.size())) != hipSuccess)
+            return fail("hipMalloc", e);
+        dev = static_cast<uint8_t *>(p);
+        enqueued = true;
+        if ((e = hipMemcpyAsync(dev, host.data(), host.size(), hipMemcpyHostToDevice, b->stream)) != hipSuccess)
+            return fail("hipMemcpyAsync H2D", e);
+        // read states at d_states, write states max_conns states further (BRB_TransformBatcher::state)
+        if ((e = brb::launch_rc4_keysetup(b->d_states, dev, reinterpret_cast<const uint64_t *>(dev + o_off),
+                                          reinterpret_cast<const uint32_t *>(dev + o_len), n, b->stream,
+                                          reinterpret_cast<const uint32_t *>(dev + o_slot),
+                                          uint64_t(b->max_conns) * sizeof(BRB_RC4_State))) != hipSuccess)
+            return fail("kernel launch", e);
+    }
+
+    // true: the part's connections are keyed.  false: they are left disabled (err says why).
+    bool finish()
+    {
+        if (enqueued) {
+            DeviceGuard g(b->dev);
+            hipError_t e = g.error();
+            if (e == hipSuccess)
+                e = hipStreamSynchronize(b->stream);
+            if (e != hipSuccess && err.empty())
+                fail(g.error() != hipSuccess ? "hipSetDevice" : "hipStreamSynchronize", e);
+            if (g.error() == hipSuccess)
+                (void)hipFree(dev);     // the stream has drained (or failed): nothing reads it any more
+        }
+        const bool ok = err.empty();
+        for (uint32_t c : conns)
+            if (ok)
+                key_installed(b, c);
+            else
+                b->enabled[c] = 0;      // its states may be half written: refused until enabled again
+        return ok;
+    }
+};
+
+}  // namespace
+
+extern "C" int BRB_TransformBatcherEnableBatch(BRB_TransformBatcher *b, const uint32_t *conns, uint64_t n, const void *keys,
+                                               const uint64_t *key_offsets, const uint32_t *key_lengths)
+{
+    brb_api::clear_err();
+    if (!b) {
+        set_err("NULL batcher");
+        return BRB_BATCH_BADARG;
+    }
+    if (n == 0)
+        return BRB_BATCH_OK;
+    if (!conns || !keys || !key_offsets || !key_lengths) {
+        set_err("NULL conns, keys, key_offsets or key_lengths");
+        return BRB_BATCH_BADARG;
+    }
+    std::vector<uint8_t> listed(b->max_conns, 0);
+    for (uint64_t i = 0; i < n; i++) {
+        if (conns[i] >= b->max_conns || key_lengths[i] == 0 || listed[conns[i]]) {
+            set_err("entry %llu: connection %u %s", (unsigned long long)i, conns[i],
+                    conns[i] >= b->max_conns ? "is out of range" : key_lengths[i] == 0 ? "has a zero key length"
+                                                                                       : "is listed twice");
+            return BRB_BATCH_BADARG;
+        }
+        if (key_offsets[i] > UINT64_MAX - key_lengths[i]) {
+            set_err("entry %llu: key offset + length wraps", (unsigned long long)i);
+            return BRB_BATCH_BADARG;
+        }
+        listed[conns[i]] = 1;
+    }
+    const uint32_t G = b->subs.empty() ? 1u : uint32_t(b->subs.size());
+    std::vector<EnablePart> parts(G);
+    for (uint32_t g = 0; g < G; g++)
+        parts[g].b = b->subs.empty() ? b : b->subs[g];
+    for (uint64_t i = 0; i < n; i++) {
+        EnablePart &p = parts[conns[i] % G];
+        p.conns.push_back(conns[i] / G);
+        p.which.push_back(i);
+    }
+    for (EnablePart &p : parts)
+        if (!p.conns.empty())
+            p.enqueue(static_cast<const uint8_t *>(keys), key_offsets, key_lengths);
+    std::string why;
+    uint32_t failed = 0;
+    for (uint32_t g = 0; g < G; g++) {
+        EnablePart &p = parts[g];
+        if (p.conns.empty() || p.finish())
+            continue;
+        ++failed;
+        why += (why.empty() ? "part " : "; part ") + std::to_string(g) + ": " + p.err;
+    }
+    if (!failed)
+        return BRB_BATCH_OK;
+    set_err("EnableBatch: %u of %u parts failed, their listed connections are left disabled (%s)", failed, G,
+            why.c_str());
+    return BRB_BATCH_NOT_DONE;
+}
 
 // A buffer of a poisoned key epoch (its connection's states went out of step in a dropped round).
 static bool poisoned(const BRB_TransformBatcher *b, const Item &it)

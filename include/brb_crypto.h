@@ -242,6 +242,35 @@ int BRB_Blowfish_EncryptBatch(const BRB_BLOWFISH_CTX *ctx, unsigned long *words,
 int BRB_Blowfish_DecryptBatch(const BRB_BLOWFISH_CTX *ctx, unsigned long *words, uint64_t n_blocks,
                               unsigned flags, void *hip_stream);
 
+/* ---- Key setup as a batch (EvAIOReqTransform_CryptoEnable, ev_kq_aio_transform.c:75-108) ------
+ * Key i = keys[key_offsets[i] .. + key_lengths[i]).  Keys may sit at any byte offset and may overlap
+ * or be shared: one key used by every record (all offsets equal) is the daemon's normal case.  Only
+ * the key bytes the reference would read are read -- RC4 indexes key[k % len] for k < 256, the first
+ * min(len, 256) bytes; Blowfish takes 72 key bytes cyclically, the first min(len, 72) -- through
+ * aligned dwords, and nothing beyond the dword holding a key's last used byte is touched.
+ * Flags and return codes as the other batch calls: BRB_BATCH_HOST copies the span of the key bytes,
+ * the offsets and the lengths in and the states / contexts out; BRB_BATCH_DEVICE (optionally
+ * BRB_BATCH_ASYNC) runs on hip_stream and copies nothing; BRB_BATCH_ALL_DEVICES (host mode) splits
+ * the keys into contiguous ranges, always, since the outputs are fixed-stride.  Neither call uses a
+ * wave-pair kernel: BRB_BATCH_FAULT never occurs.  n_keys == 0 returns 1 and touches nothing.  A
+ * NULL pointer with n_keys > 0 returns -1; so does, in host mode, any key_lengths[i] == 0; nothing is
+ * written.  Device mode validates no length: a zero length is the caller's broken promise (the
+ * device-mode contract above); its record reads no key byte, gets the schedule of one zero byte, and
+ * no memory outside that record's own state or context is touched.  Device mode: states must be
+ * 4-byte aligned (as the RC4 calls assume), ctxs 8-byte aligned.  No CPU fallback: without a usable
+ * device the calls return 0 with a LastError. */
+
+/* states[i] (264 bytes each, contiguous) = the state EvAIOReqTransform_CryptoEnable leaves: all 264
+ * bytes zeroed, then BRB_RC4_Init(&states[i], key i).  All 264 bytes are written (perm,
+ * index1 = index2 = 0, six zero bytes). */
+int BRB_RC4_InitBatch(BRB_RC4_State *states, const void *keys, const uint64_t *key_offsets,
+                      const uint32_t *key_lengths, uint64_t n_keys, unsigned flags, void *hip_stream);
+
+/* ctxs[i] (8336 bytes each, contiguous) = BRB_Blowfish_Init(&ctxs[i], key i), every 64-bit entry of P
+ * and S bit for bit (blowfish.c:382-443 with the 64-bit carries of _F). */
+int BRB_Blowfish_InitBatch(BRB_BLOWFISH_CTX *ctxs, const void *keys, const uint64_t *key_offsets,
+                           const uint32_t *key_lengths, uint64_t n_keys, unsigned flags, void *hip_stream);
+
 /* ---- RC4 and the RC4+MD5 frame of the comm transform -------------------------
  * One stream per connection; states[i] is that connection's BRB_RC4_State (an array of n
  * contiguous 264-byte states) and advances exactly as the scalar calls would.  Streams of one
@@ -319,6 +348,20 @@ BRB_TransformBatcher *BRB_TransformBatcherCreate(uint32_t max_conns, uint64_t ma
 void BRB_TransformBatcherDestroy(BRB_TransformBatcher *b);
 /* EvAIOReqTransform_CryptoEnable (ev_kq_aio_transform.c:71-105): both states of `conn` = BRB_RC4_Init(key). */
 int BRB_TransformBatcherEnable(BRB_TransformBatcher *b, uint32_t conn, const void *key, int key_sz);
+/* Enable for n connections in one call (host pointers; keys as in BRB_RC4_InitBatch, connection
+ * conns[i] gets key i).  One H2D copy of the key bytes and index arrays, one kernel that writes both
+ * the read and the write state of every listed connection straight into the batcher's state arrays,
+ * one stream synchronisation -- on the batcher's own stream, so on a pipelined batcher it orders
+ * behind a round FlushAsync left running, as Enable's copies do.  Returns -1, with nothing changed,
+ * for a NULL argument, a connection id >= max_conns, a zero key length or a connection listed twice
+ * (two lanes would write one state); n == 0 returns 1.  After success every listed connection is as
+ * after Enable: enabled, its key epoch incremented (a poisoned connection is re-keyed).  All-devices
+ * batcher: the list is split by conn % G into the parts, and every part is enqueued before any is
+ * waited for.  On a device error the call returns 0, LastError names the parts that failed, and the
+ * listed connections of those parts are left disabled (Read/Write refuse them until they are enabled
+ * again); the other parts' connections are enabled. */
+int BRB_TransformBatcherEnableBatch(BRB_TransformBatcher *b, const uint32_t *conns, uint64_t n,
+                                    const void *keys, const uint64_t *key_offsets, const uint32_t *key_lengths);
 /* Read/Write may run concurrently on several threads (the reference's mt_engine, ev_kq_base.c:95)
  * as long as each connection is submitted from one thread; results come back in each connection's
  * order.  Flush/FlushAsync/Enable must not overlap them.  A thread reserves slots and arena bytes in
