@@ -43,6 +43,11 @@ from .crypto import (  # noqa: F401
     blowfish_decrypt_batch,
     blowfish_encrypt_batch,
     blowfish_init,
+    blowfish_contexts,
+    blowfish_encrypt_batch_keyed,
+    blowfish_decrypt_batch_keyed,
+    membuf_encrypt_batch,
+    membuf_decrypt_batch,
     device_count,
     exported_symbols,
     gpu_available,
@@ -83,4 +88,6 @@ __all__ = [
     "HostRegion", "BATCHER_ZERO_COPY", "BATCHER_PIPELINED", "BATCH_ALL_DEVICES", "device_count",
     "BATCH_DROPPED", "TRANSFORM_DROPPED", "BATCHER_ALL_DEVICES", "TestOption", "test_option", "async_fault_check",
     "rc4_init_batch", "blowfish_init_batch", "pack_keys", "unpack_keys", "BLOWFISH_CTX_BYTES",
+    "blowfish_contexts", "blowfish_encrypt_batch_keyed", "blowfish_decrypt_batch_keyed", "membuf_encrypt_batch",
+    "membuf_decrypt_batch",
 ]

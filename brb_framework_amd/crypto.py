@@ -102,6 +102,18 @@ _SIGNATURES = [
      [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint, ctypes.c_void_p]),
     ("BRB_Blowfish_DecryptBatch", ctypes.c_int,
      [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint, ctypes.c_void_p]),
+    ("BRB_Blowfish_EncryptBatchKeyed", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+      ctypes.c_uint64, ctypes.c_uint, ctypes.c_void_p]),
+    ("BRB_Blowfish_DecryptBatchKeyed", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+      ctypes.c_uint64, ctypes.c_uint, ctypes.c_void_p]),
+    ("BRB_MemBufferEncryptBatch", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
+      ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint, ctypes.c_void_p]),
+    ("BRB_MemBufferDecryptBatch", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
+      ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint, ctypes.c_void_p]),
     ("BRB_RC4_InitBatch", ctypes.c_int,
      [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint,
       ctypes.c_void_p]),
@@ -416,6 +428,46 @@ def blowfish_decrypt_batch(ctx, words, n_blocks=None, stream=None, async_=False,
     return _bf(lib().BRB_Blowfish_DecryptBatch, ctx, words, n_blocks, stream, async_, all_devices)
 
 
+def blowfish_contexts(ctxs) -> np.ndarray:
+    """A list of BRB_BLOWFISH_CTX -> the (n, 8336) uint8 array the keyed calls take as `ctxs`."""
+    return np.frombuffer(b"".join(blowfish_ctx_bytes(c) for c in ctxs), np.uint8).reshape(len(ctxs), BLOWFISH_CTX_BYTES).copy()
+
+
+def _bf_keyed(fn, ctxs, words, word_offsets, block_counts, ctx_index, stream, async_, all_devices):
+    """words: uint64 numpy array (host) or int64/uint64 CUDA tensor (device); word_offsets uint64[n] (in 8-byte
+    words), block_counts uint32[n], ctx_index uint32[n] or None, of the same kind.  ctxs: (n_ctx, 8336) uint8
+    of that kind too (a blowfish_init_batch result as it stands), or a list of BRB_BLOWFISH_CTX / a numpy
+    array, which device mode uploads for you."""
+    if isinstance(ctxs, (list, tuple)):
+        ctxs = blowfish_contexts(ctxs)
+    flags, h = _mode(words, stream, async_, all_devices)
+    if (flags & BATCH_DEVICE) and not _is_torch(ctxs):
+        import torch
+        ctxs = torch.from_numpy(np.ascontiguousarray(ctxs)).to(words.device)
+    _same_kind(words, ctxs, word_offsets, block_counts, ctx_index)
+    n = len(word_offsets)
+    if len(block_counts) != n or (ctx_index is not None and len(ctx_index) != n):
+        raise ValueError("word_offsets, block_counts and ctx_index differ in length")
+    _check(fn(_ptr(ctxs), _nbytes(ctxs) // BLOWFISH_CTX_BYTES, _ptr(ctx_index), _ptr(words), _ptr(word_offsets),
+              _ptr(block_counts), n, flags, h), fn.__name__)
+    return words
+
+
+def blowfish_encrypt_batch_keyed(ctxs, words, word_offsets, block_counts, ctx_index=None, stream=None, async_=False,
+                                 all_devices=False):
+    """BRB_Blowfish_EncryptBatchKeyed: record i = block_counts[i] (xl, xr) pairs at words[word_offsets[i]:],
+    encrypted in place with ctxs[ctx_index[i]] (ctx_index None: ctxs[i]).  Returns words."""
+    return _bf_keyed(lib().BRB_Blowfish_EncryptBatchKeyed, ctxs, words, word_offsets, block_counts, ctx_index, stream,
+                     async_, all_devices)
+
+
+def blowfish_decrypt_batch_keyed(ctxs, words, word_offsets, block_counts, ctx_index=None, stream=None, async_=False,
+                                 all_devices=False):
+    """BRB_Blowfish_DecryptBatchKeyed (see blowfish_encrypt_batch_keyed)."""
+    return _bf_keyed(lib().BRB_Blowfish_DecryptBatchKeyed, ctxs, words, word_offsets, block_counts, ctx_index, stream,
+                     async_, all_devices)
+
+
 def device_count() -> int:
     """BRB_CryptoGPU_DeviceCount (0 without a usable device)."""
     return int(lib().BRB_CryptoGPU_DeviceCount())
@@ -565,6 +617,42 @@ def membuf_encrypt(buf, size, seed, offset=0, stream=None):
 def membuf_decrypt(buf, size, seed, offset=0, stream=None):
     """BRB_MemBufferDecrypt in place; returns the new MemBuffer size."""
     return _membuf(lib().BRB_MemBufferDecrypt, buf, size, seed, offset, stream, True)
+
+
+def _membuf_batch(fn, data, buf_offsets, sizes, seeds, offsets, seed_index, new_sizes, stream, all_devices):
+    seeds = np.ascontiguousarray(np.atleast_1d(seeds), np.uint32)      # always host memory: a parameter
+    n = len(buf_offsets)
+    if len(sizes) != n or (offsets is not None and len(offsets) != n) or (seed_index is not None and len(seed_index) != n):
+        raise ValueError("buf_offsets, sizes, offsets and seed_index differ in length")
+    if new_sizes is None:
+        if _is_torch(data):
+            import torch
+            new_sizes = torch.zeros(n, dtype=torch.int64, device=data.device)
+        else:
+            new_sizes = np.zeros(n, np.uint64)
+    _same_kind(data, buf_offsets, sizes, offsets, seed_index, new_sizes)
+    flags, h = _mode(data, stream, False, all_devices)
+    _check(fn(_ptr(data), _ptr(buf_offsets), _ptr(sizes), _ptr(offsets), _ptr(seeds), len(seeds), _ptr(seed_index), n,
+              _ptr(new_sizes), flags, h), fn.__name__)
+    return new_sizes
+
+
+def membuf_encrypt_batch(data, buf_offsets, sizes, seeds, offsets=None, seed_index=None, new_sizes=None, stream=None,
+                         all_devices=False):
+    """BRB_MemBufferEncryptBatch in place: buffer i = data[buf_offsets[i]:] with MemBuffer size sizes[i], offset
+    argument offsets[i] (None: 0) and seed seeds[seed_index[i]] (seed_index None: one seed for all, or one per
+    buffer).  buf_offsets, sizes, offsets uint64[n], seed_index uint32[n]: numpy with numpy data, CUDA tensors
+    (int64 / int32) with a CUDA tensor; seeds is a host sequence either way.  The caller has grown every buffer
+    to membuf_span.  Returns new_sizes (uint64[n] numpy, or an int64 tensor)."""
+    return _membuf_batch(lib().BRB_MemBufferEncryptBatch, data, buf_offsets, sizes, seeds, offsets, seed_index, new_sizes,
+                         stream, all_devices)
+
+
+def membuf_decrypt_batch(data, buf_offsets, sizes, seeds, offsets=None, seed_index=None, new_sizes=None, stream=None,
+                         all_devices=False):
+    """BRB_MemBufferDecryptBatch in place (see membuf_encrypt_batch); returns new_sizes."""
+    return _membuf_batch(lib().BRB_MemBufferDecryptBatch, data, buf_offsets, sizes, seeds, offsets, seed_index, new_sizes,
+                         stream, all_devices)
 
 
 # ---- base64 (SURVEY §8 f4) -------------------------------------------------------------------------

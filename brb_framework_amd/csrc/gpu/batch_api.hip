@@ -464,7 +464,8 @@ struct Staging {
 
 // [lo, hi) covered by ranges offsets[i] .. + lengths[i] + extra (empty ranges ignored); false (and
 // the error set) when a range wraps the address space
-bool span_of(const uint64_t *offs, const uint32_t *lens, uint64_t n, uint64_t extra, uint64_t &lo, uint64_t &hi)
+template <typename LenT>   // uint32_t, or uint64_t for the keyed Blowfish records (16 bytes x a uint32 block count)
+bool span_of(const uint64_t *offs, const LenT *lens, uint64_t n, uint64_t extra, uint64_t &lo, uint64_t &hi)
 {
     lo = UINT64_MAX;
     hi = 0;
@@ -499,7 +500,8 @@ std::vector<uint64_t> rebase(const uint64_t *offs, uint64_t n, uint64_t lo)
 // otherwise a part would write back bytes of another part's ranges.  Streams of different
 // connections are disjoint by contract; ranges in submission order give disjoint spans.  Ranges
 // in any other order run on the calling thread's device (same results, one device).
-bool parts_disjoint(const uint64_t *offs, const uint32_t *lens, uint64_t n, uint64_t extra, const uint32_t *lens_out = nullptr)
+template <typename LenT>
+bool parts_disjoint(const uint64_t *offs, const LenT *lens, uint64_t n, uint64_t extra, const LenT *lens_out = nullptr)
 {
     const int G = brb_host::split_parts();
     if (G <= 1 || n < uint64_t(G))
@@ -1090,6 +1092,242 @@ int membuf_crypt(void *buf, unsigned long size, unsigned int seed, unsigned long
     return rc;
 }
 
+// ---- Blowfish ECB with a context per record (blowfish_keyed_kernels.hip) -----------------------
+// No wave-pair kernel: no fault word.
+int blowfish_keyed(const BRB_BLOWFISH_CTX *ctxs, uint64_t n_ctx, const uint32_t *ctx_index, unsigned long *words,
+                   const uint64_t *woffs, const uint32_t *counts, uint64_t n, unsigned flags, void *stream, bool decrypt)
+{
+    t_err.clear();
+    if (n == 0)
+        return BRB_BATCH_OK;
+    if (!ctxs || !words || !woffs || !counts) {
+        set_err("NULL ctxs, words, word_offsets or block_counts");
+        return BRB_BATCH_BADARG;
+    }
+    if (!flags_ok(flags))
+        return BRB_BATCH_BADARG;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    hipError_t e;
+    if (flags & BRB_BATCH_DEVICE) {
+        if ((reinterpret_cast<uintptr_t>(words) | reinterpret_cast<uintptr_t>(ctxs)) & 7) {
+            set_err("device mode needs words and ctxs 8-byte aligned");
+            return BRB_BATCH_BADARG;
+        }
+        if (int ok = device_ok(); ok != BRB_BATCH_OK)
+            return ok;
+        if ((e = brb::launch_blowfish_keyed(reinterpret_cast<const uint64_t *>(ctxs), ctx_index,
+                                            reinterpret_cast<uint64_t *>(words), woffs, counts, n, decrypt, nullptr,
+                                            s)) != hipSuccess)
+            return fail_hip("kernel launch", e);
+        return finish(s, flags);
+    }
+    // host mode: every list is host memory and is checked before anything runs
+    if (!ctx_index && n_ctx != n) {
+        set_err("ctx_index is NULL and n_ctx (%llu) != n_rec (%llu)", (unsigned long long)n_ctx, (unsigned long long)n);
+        return BRB_BATCH_BADARG;
+    }
+    std::vector<uint64_t> boff(n), blen(n);          // the records in bytes
+    for (uint64_t i = 0; i < n; i++) {
+        if (ctx_index && ctx_index[i] >= n_ctx) {
+            set_err("record %llu: ctx_index %u out of range (%llu contexts)", (unsigned long long)i, ctx_index[i],
+                    (unsigned long long)n_ctx);
+            return BRB_BATCH_BADARG;
+        }
+        if (woffs[i] > UINT64_MAX / 8) {
+            set_err("record %llu: word offset %llu wraps", (unsigned long long)i, (unsigned long long)woffs[i]);
+            return BRB_BATCH_BADARG;
+        }
+        boff[i] = 8 * woffs[i];
+        blen[i] = 16 * uint64_t(counts[i]);
+    }
+    uint64_t lo, hi;
+    if (!span_of(boff.data(), blen.data(), n, 0, lo, hi))
+        return BRB_BATCH_BADARG;
+    if (int ok = device_ok(); ok != BRB_BATCH_OK)
+        return ok;
+    if (flags & BRB_BATCH_ALL_DEVICES) {   // records are written back: their spans must not interleave
+        flags &= ~BRB_BATCH_ALL_DEVICES;
+        if (parts_disjoint(boff.data(), blen.data(), n, 0))
+            return brb_host::split_devices(n, [&](int, uint64_t a, uint64_t b) {
+                return blowfish_keyed(ctx_index ? ctxs : ctxs + a, ctx_index ? n_ctx : b - a,
+                                      ctx_index ? ctx_index + a : nullptr, words, woffs + a, counts + a, b - a, flags,
+                                      nullptr, decrypt);
+            });
+    }
+    // the contexts the records with blocks name, compacted in index order (runs of neighbours = one copy)
+    std::vector<uint32_t> cidx(n, 0);
+    std::vector<uint64_t> used;
+    used.reserve(n);
+    for (uint64_t i = 0; i < n; i++)
+        if (counts[i])
+            used.push_back(ctx_index ? ctx_index[i] : i);
+    std::sort(used.begin(), used.end());
+    used.erase(std::unique(used.begin(), used.end()), used.end());
+    for (uint64_t i = 0; i < n; i++)
+        if (counts[i])
+            cidx[i] = uint32_t(std::lower_bound(used.begin(), used.end(), ctx_index ? ctx_index[i] : i) - used.begin());
+    std::vector<uint64_t> roff(n);
+    for (uint64_t i = 0; i < n; i++)
+        roff[i] = counts[i] ? (boff[i] - lo) / 8 : 0;   // lo is a record's start: the differences are whole words
+    Staging st;
+    uint8_t *raw = reinterpret_cast<uint8_t *>(words) + lo;
+    const size_t i_w = st.add(raw, raw, size_t(hi - lo));
+    const size_t i_o = st.add(roff.data(), nullptr, 8 * n);
+    const size_t i_c = st.add(counts, nullptr, 4 * n);
+    const size_t i_x = st.add(cidx.data(), nullptr, 4 * n);
+    const size_t i_ctx = st.add(nullptr, nullptr, sizeof(BRB_BLOWFISH_CTX) * std::max<size_t>(used.size(), 1));
+    int rc = st.upload(s);
+    for (size_t a = 0; rc == BRB_BATCH_OK && a < used.size();) {
+        size_t b = a + 1;
+        while (b < used.size() && used[b] == used[b - 1] + 1)
+            b++;
+        if ((e = hipMemcpyAsync(st.dev(i_ctx) + sizeof(BRB_BLOWFISH_CTX) * a, ctxs + used[a],
+                                sizeof(BRB_BLOWFISH_CTX) * (b - a), hipMemcpyHostToDevice, s)) != hipSuccess)
+            rc = fail_hip("hipMemcpyAsync H2D", e);
+        a = b;
+    }
+    if (rc == BRB_BATCH_OK &&
+        (e = brb::launch_blowfish_keyed(reinterpret_cast<const uint64_t *>(st.dev(i_ctx)),
+                                        reinterpret_cast<const uint32_t *>(st.dev(i_x)),
+                                        reinterpret_cast<uint64_t *>(st.dev(i_w)),
+                                        reinterpret_cast<const uint64_t *>(st.dev(i_o)),
+                                        reinterpret_cast<const uint32_t *>(st.dev(i_c)), n, decrypt, nullptr, s)) != hipSuccess)
+        rc = fail_hip("kernel launch", e);
+    if (rc == BRB_BATCH_OK)
+        return st.download(s);
+    (void)hipStreamSynchronize(s);
+    return rc;
+}
+
+// ---- MemBuffer Blowfish as a batch ---------------------------------------------------------------
+// One key-setup launch for the n_seeds seeds into the thread's workspace, a plan (host mode: on the
+// host; device mode: a kernel), one keyed launch, one synchronisation.  The contexts live in the
+// workspace, so device mode synchronises too (ASYNC is ignored, as by the single calls).
+int membuf_batch(void *data, const uint64_t *buf_offsets, const uint64_t *sizes, const uint64_t *offsets,
+                 const unsigned int *seeds, uint64_t n_seeds, const uint32_t *seed_index, uint64_t n, uint64_t *new_sizes,
+                 unsigned flags, void *stream, bool decrypt)
+{
+    t_err.clear();
+    if (n == 0)
+        return BRB_BATCH_OK;
+    if (!data || !buf_offsets || !sizes || !seeds || !new_sizes) {
+        set_err("NULL data, buf_offsets, sizes, seeds or new_sizes");
+        return BRB_BATCH_BADARG;
+    }
+    if (!flags_ok(flags))
+        return BRB_BATCH_BADARG;
+    if (n_seeds == 0 || (!seed_index && n_seeds != 1 && n_seeds != n)) {
+        set_err("n_seeds %llu with %s seed_index (%llu buffers)", (unsigned long long)n_seeds, seed_index ? "a" : "NULL",
+                (unsigned long long)n);
+        return BRB_BATCH_BADARG;
+    }
+    const bool device = (flags & BRB_BATCH_DEVICE) != 0;
+    if (device && (reinterpret_cast<uintptr_t>(data) & 7)) {
+        set_err("device mode needs data 8-byte aligned (and every buf_offsets[i] + offsets[i])");
+        return BRB_BATCH_BADARG;
+    }
+    // host mode: the plan, checked before anything runs
+    std::vector<uint64_t> woffs, starts;
+    std::vector<uint32_t> counts, idx;
+    std::vector<uint8_t> stage;
+    if (!device) {
+        woffs.resize(n);
+        starts.resize(n);
+        counts.resize(n);
+        idx.resize(n);
+        uint64_t total = 0;
+        for (uint64_t i = 0; i < n; i++) {
+            const uint64_t off = offsets ? offsets[i] : 0;
+            if (decrypt && sizes[i] < off) {
+                set_err("buffer %llu: size %llu < offset %llu (the reference would walk ~2^61 words)", (unsigned long long)i,
+                        (unsigned long long)sizes[i], (unsigned long long)off);
+                return BRB_BATCH_BADARG;
+            }
+            const uint64_t si = seed_index ? uint64_t(seed_index[i]) : (n_seeds == 1 ? 0 : i);
+            if (si >= n_seeds) {
+                set_err("buffer %llu: seed_index %llu out of range (%llu seeds)", (unsigned long long)i,
+                        (unsigned long long)si, (unsigned long long)n_seeds);
+                return BRB_BATCH_BADARG;
+            }
+            if (!decrypt && sizes[i] > UINT64_MAX - off) {
+                set_err("buffer %llu: size + offset wraps", (unsigned long long)i);
+                return BRB_BATCH_BADARG;
+            }
+            const uint64_t pairs = (((decrypt ? sizes[i] - off : sizes[i] + off) >> 3) + 3) >> 1;
+            if (pairs > UINT32_MAX) {
+                set_err("buffer %llu: %llu pairs (at most 2^32 - 1 per buffer)", (unsigned long long)i,
+                        (unsigned long long)pairs);
+                return BRB_BATCH_BADARG;
+            }
+            starts[i] = buf_offsets[i] + off;
+            woffs[i] = total / 8;
+            counts[i] = uint32_t(pairs);
+            idx[i] = uint32_t(si);
+            total += 16 * pairs;
+        }
+        stage.resize(std::max<uint64_t>(total, 16));   // 8-byte aligned staging whatever the buffers' alignment
+    }
+    if (int ok = device_ok(); ok != BRB_BATCH_OK)
+        return ok;
+    // keys (mem_buf.c:1511-1515) and the reference's keyLen quirk (:1528 vs :1582)
+    std::vector<unsigned int> keys(16 * n_seeds);
+    std::vector<uint64_t> koffs(n_seeds);
+    std::vector<uint32_t> klens(n_seeds, decrypt ? 64u : 4u);
+    for (uint64_t k = 0; k < n_seeds; k++) {
+        BRB_MemBufferKey(seeds[k], &keys[16 * k]);
+        koffs[k] = 64 * k;
+    }
+    if (!device)
+        for (uint64_t i = 0; i < n; i++)
+            memcpy(stage.data() + 8 * woffs[i], static_cast<const uint8_t *>(data) + starts[i], 16 * size_t(counts[i]));
+    std::vector<uint32_t> done(device || !decrypt ? 0 : n);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    hipError_t e;
+    Staging st;
+    const size_t i_k = st.add(keys.data(), nullptr, 64 * n_seeds);
+    const size_t i_ko = st.add(koffs.data(), nullptr, 8 * n_seeds);
+    const size_t i_kl = st.add(klens.data(), nullptr, 4 * n_seeds);
+    const size_t i_ctx = st.add(nullptr, nullptr, sizeof(BRB_BLOWFISH_CTX) * n_seeds);
+    const size_t i_o = st.add(device ? nullptr : woffs.data(), nullptr, 8 * n);
+    const size_t i_c = st.add(device ? nullptr : counts.data(), nullptr, 4 * n);
+    const size_t i_x = st.add(device ? nullptr : idx.data(), nullptr, 4 * n);
+    const size_t i_d = st.add(nullptr, done.empty() ? nullptr : done.data(), 4 * n);
+    const size_t i_w = device ? 0 : st.add(stage.data(), stage.data(), stage.size());
+    int rc = st.upload(s);
+    uint64_t *w = device ? static_cast<uint64_t *>(data) : reinterpret_cast<uint64_t *>(st.dev(i_w));
+    uint64_t *d_o = reinterpret_cast<uint64_t *>(st.dev(i_o));
+    uint32_t *d_c = reinterpret_cast<uint32_t *>(st.dev(i_c)), *d_x = reinterpret_cast<uint32_t *>(st.dev(i_x));
+    uint32_t *d_d = reinterpret_cast<uint32_t *>(st.dev(i_d));
+    if (rc == BRB_BATCH_OK &&
+        (e = brb::launch_blowfish_keysetup(reinterpret_cast<uint64_t *>(st.dev(i_ctx)), st.dev(i_k),
+                                           reinterpret_cast<const uint64_t *>(st.dev(i_ko)),
+                                           reinterpret_cast<const uint32_t *>(st.dev(i_kl)), n_seeds, s)) != hipSuccess)
+        rc = fail_hip("kernel launch", e);
+    if (rc == BRB_BATCH_OK && device &&
+        (e = brb::launch_membuf_plan(buf_offsets, sizes, offsets, seed_index, n_seeds, n, decrypt, d_o, d_c, d_x, new_sizes,
+                                     s)) != hipSuccess)
+        rc = fail_hip("kernel launch", e);
+    if (rc == BRB_BATCH_OK &&
+        (e = brb::launch_blowfish_keyed(reinterpret_cast<const uint64_t *>(st.dev(i_ctx)), d_x, w, d_o, d_c, n, decrypt,
+                                        decrypt ? d_d : nullptr, s)) != hipSuccess)
+        rc = fail_hip("kernel launch", e);
+    if (rc == BRB_BATCH_OK && device && decrypt &&
+        (e = brb::launch_membuf_finish(d_d, offsets, n, new_sizes, s)) != hipSuccess)
+        rc = fail_hip("kernel launch", e);
+    if (rc == BRB_BATCH_OK)
+        rc = st.download(s);        // host mode: the staged words (and the stops) back; always: synchronise
+    else
+        (void)hipStreamSynchronize(s);
+    if (rc != BRB_BATCH_OK || device)
+        return rc;
+    for (uint64_t i = 0; i < n; i++) {
+        const uint64_t did = decrypt ? done[i] : counts[i];    // bytes from the stop onward are not written
+        memcpy(static_cast<uint8_t *>(data) + starts[i], stage.data() + 8 * woffs[i], 16 * size_t(did));
+        new_sizes[i] = 16 * did + (offsets ? offsets[i] : 0);
+    }
+    return rc;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1181,6 +1419,36 @@ int BRB_Blowfish_DecryptBatch(const BRB_BLOWFISH_CTX *ctx, unsigned long *words,
                               void *hip_stream)
 {
     return blowfish_batch(ctx, words, n_blocks, flags, hip_stream, true);
+}
+
+int BRB_Blowfish_EncryptBatchKeyed(const BRB_BLOWFISH_CTX *ctxs, uint64_t n_ctx, const uint32_t *ctx_index,
+                                   unsigned long *words, const uint64_t *word_offsets, const uint32_t *block_counts,
+                                   uint64_t n_rec, unsigned flags, void *hip_stream)
+{
+    return blowfish_keyed(ctxs, n_ctx, ctx_index, words, word_offsets, block_counts, n_rec, flags, hip_stream, false);
+}
+
+int BRB_Blowfish_DecryptBatchKeyed(const BRB_BLOWFISH_CTX *ctxs, uint64_t n_ctx, const uint32_t *ctx_index,
+                                   unsigned long *words, const uint64_t *word_offsets, const uint32_t *block_counts,
+                                   uint64_t n_rec, unsigned flags, void *hip_stream)
+{
+    return blowfish_keyed(ctxs, n_ctx, ctx_index, words, word_offsets, block_counts, n_rec, flags, hip_stream, true);
+}
+
+int BRB_MemBufferEncryptBatch(void *data, const uint64_t *buf_offsets, const uint64_t *sizes, const uint64_t *offsets,
+                              const unsigned int *seeds, uint64_t n_seeds, const uint32_t *seed_index, uint64_t n_buf,
+                              uint64_t *new_sizes, unsigned flags, void *hip_stream)
+{
+    return membuf_batch(data, buf_offsets, sizes, offsets, seeds, n_seeds, seed_index, n_buf, new_sizes, flags, hip_stream,
+                        false);
+}
+
+int BRB_MemBufferDecryptBatch(void *data, const uint64_t *buf_offsets, const uint64_t *sizes, const uint64_t *offsets,
+                              const unsigned int *seeds, uint64_t n_seeds, const uint32_t *seed_index, uint64_t n_buf,
+                              uint64_t *new_sizes, unsigned flags, void *hip_stream)
+{
+    return membuf_batch(data, buf_offsets, sizes, offsets, seeds, n_seeds, seed_index, n_buf, new_sizes, flags, hip_stream,
+                        true);
 }
 
 int BRB_RC4_InitBatch(BRB_RC4_State *states, const void *keys, const uint64_t *key_offsets, const uint32_t *key_lengths,
@@ -1306,7 +1574,8 @@ extern "C" int BRB_CryptoGPU_TestOption(const char *name, int value, int *old)
                  {"line_slots", brb_opt::kLineSlots, 0, 3},
                  {"rc4md5_pair", brb_opt::kRc4Pair, 0, 1},
                  {"rc4_pair", brb_opt::kRc4CryptPair, 0, 1},
-                 {"pair_stall", brb_opt::kPairStall, 0, 1}};
+                 {"pair_stall", brb_opt::kPairStall, 0, 1},
+                 {"bf_keyed", brb_opt::kBfKeyed, 0, 2}};
     if (!name) {
         set_err("NULL option name");
         return BRB_BATCH_BADARG;

@@ -22,6 +22,21 @@ hipError_t launch_blowfish(const uint64_t *ctx_dev, uint64_t *words, uint64_t n_
 // *first = min(*first, index of the first block (xl, xr) with a zero word); *first preset by the caller
 hipError_t launch_first_zero_pair(const uint64_t *words, uint64_t n_blocks, unsigned long long *first, hipStream_t s);
 
+// Blowfish ECB with a context per record (blowfish_keyed_kernels.hip): record i = counts[i] blocks at
+// words + woffs[i] (8-byte words), keyed by ctxs[ctx_index ? ctx_index[i] : i] (1042 qwords each).
+// blocks_done != nullptr (decrypt only): the MemBuffer stop -- record i is decrypted up to its first
+// block with a zero word and blocks_done[i] = the blocks decrypted.
+hipError_t launch_blowfish_keyed(const uint64_t *ctxs, const uint32_t *ctx_index, uint64_t *words, const uint64_t *woffs,
+                                 const uint32_t *counts, uint64_t n_rec, bool decrypt, uint32_t *blocks_done,
+                                 hipStream_t s);
+// MemBuffer batch, device mode: buffer i -> woffs[i] (words from data), counts[i] (pairs), idx[i] (its
+// seed's context); encrypt also new_sizes[i].  finish (decrypt): new_sizes[i] = 16 done[i] + offsets[i].
+hipError_t launch_membuf_plan(const uint64_t *buf_offsets, const uint64_t *sizes, const uint64_t *offsets,
+                              const uint32_t *seed_index, uint64_t n_seeds, uint64_t n, bool decrypt, uint64_t *woffs,
+                              uint32_t *counts, uint32_t *idx, uint64_t *new_sizes, hipStream_t s);
+hipError_t launch_membuf_finish(const uint32_t *done, const uint64_t *offsets, uint64_t n, uint64_t *new_sizes,
+                                hipStream_t s);
+
 // MD5 of segment lists (md5_seg_kernels.hip): record r = segments first[r] .. first[r + 1] - 1
 hipError_t launch_md5_segments(const uint8_t *data, const uint64_t *soff, const uint32_t *slen, const uint64_t *first,
                                uint64_t n_rec, uint8_t *out, hipStream_t s);

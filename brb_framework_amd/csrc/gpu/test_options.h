@@ -28,10 +28,12 @@ enum Opt {
     kPairStall = 13,    // 1: inject a protocol fault into the segment-digest, MetaData, RC4-pass and frame/open wave pairs
                         // (the first workgroup's first pair never hands over its first plan / block), so the
                         // tests see a bounded wait give up and the call report it (pair_fault.h); 0: off
-    kCount = 14
+    kBfKeyed = 14,      // keyed Blowfish ECB (blowfish_keyed_kernels.hip): 0 spread fill, 2 blocks per lane (default);
+                        // 1 the plain fill; 2 one block per lane.  The MemBuffer decrypt stop always runs the default
+    kCount = 15
 };
 
-inline std::atomic<int> g_opt[kCount] = {-1, 1, 1, 1, 0, -1, 0, 0, 2, 2, 0, 1, 1, 0};
+inline std::atomic<int> g_opt[kCount] = {-1, 1, 1, 1, 0, -1, 0, 0, 2, 2, 0, 1, 1, 0, 0};
 
 inline int get(Opt o) { return g_opt[o].load(std::memory_order_relaxed); }
 

@@ -45,6 +45,32 @@ def kv_decrypt(data: bytes, stream=None) -> bytes:
     return b[:n].tobytes()
 
 
+def _batch(datas, fn):
+    """One MemBuffer batch call over `datas` (bytes each), every buffer grown and zero-filled as _mb does."""
+    datas = [bytes(d) for d in datas]
+    if not datas:
+        return []
+    sizes = np.array([len(d) for d in datas], np.uint64)
+    room = [(max(len(d), crypto.membuf_span(len(d))) + 16 + 15) // 16 * 16 for d in datas]
+    offs = np.zeros(len(datas), np.uint64)
+    offs[1:] = np.cumsum(room[:-1], dtype=np.uint64)
+    b = np.zeros(sum(room), np.uint8)
+    for o, d in zip(offs, datas):
+        b[int(o): int(o) + len(d)] = np.frombuffer(d, np.uint8)
+    new = fn(b, offs, sizes, [KV_SEED])
+    return [b[int(o): int(o) + int(n)].tobytes() for o, n in zip(offs, new)]
+
+
+def encrypt_texts(texts) -> list:
+    """kv_encrypt of every text, in one BRB_MemBufferEncryptBatch call (one key setup, one launch)."""
+    return _batch(texts, crypto.membuf_encrypt_batch)
+
+
+def decrypt_files(blobs) -> list:
+    """kv_decrypt of every file's bytes, in one BRB_MemBufferDecryptBatch call."""
+    return _batch(blobs, crypto.membuf_decrypt_batch)
+
+
 def kv_write_file(path, pairs, enc: bool = True, without_quotes: bool = False) -> int:
     """KVWriteToFile (key_value.c:464-479).  Returns 1 like the reference."""
     text = kv_assemble(pairs, without_quotes)

@@ -242,6 +242,32 @@ int BRB_Blowfish_EncryptBatch(const BRB_BLOWFISH_CTX *ctx, unsigned long *words,
 int BRB_Blowfish_DecryptBatch(const BRB_BLOWFISH_CTX *ctx, unsigned long *words, uint64_t n_blocks,
                               unsigned flags, void *hip_stream);
 
+/* Blowfish ECB in place with a context per record: the reference keeps a Blowfish context per
+ * connection and direction (CommEvCryptoInfo, libbrb_ev_comm.h:206-236), BRB_Blowfish_InitBatch builds
+ * them, and these calls use them, n_rec records in one launch.  Record i is block_counts[i] blocks
+ * (pairs of 64-bit words) starting at words + word_offsets[i] -- an offset in 8-byte words, so a record
+ * may start at 8 mod 16 -- keyed by ctxs[ctx_index ? ctx_index[i] : i] (n_ctx contexts of 8336 bytes,
+ * contiguous).  Every word equals BRB_Blowfish_Encrypt/Decrypt with that context, bit for bit in all 64
+ * bits.  Records must not overlap each other; words between records keep their values; a record of 0
+ * blocks touches nothing (neither its words nor its context).  Flags and return codes as the other
+ * batch calls.  BRB_BATCH_HOST: ctx_index[i] >= n_ctx, or a NULL ctx_index with n_ctx != n_rec, returns
+ * -1 with nothing written; the span of the records is staged in both directions (words at any byte
+ * alignment) and the contexts the records name are uploaded.  BRB_BATCH_DEVICE (optionally
+ * BRB_BATCH_ASYNC) validates nothing but the alignment: words and ctxs must be 8-byte aligned (-1
+ * otherwise); it runs on hip_stream and needs no workspace.  BRB_BATCH_ALL_DEVICES (host mode) splits
+ * the records into contiguous ranges only when those ranges' spans do not interleave (as the RC4
+ * calls), each part uploading the contexts its records name; otherwise the call runs on the calling
+ * thread's device.  n_rec == 0 returns 1; a NULL pointer with n_rec > 0 returns -1 (ctx_index may be
+ * NULL).  No wave-pair kernel: BRB_BATCH_FAULT never occurs.  The 64 lanes of a record work on it alone:
+ * one record far longer than the others of its group of 16 holds the group up, so long single-key
+ * buffers belong to BRB_Blowfish_EncryptBatch. */
+int BRB_Blowfish_EncryptBatchKeyed(const BRB_BLOWFISH_CTX *ctxs, uint64_t n_ctx, const uint32_t *ctx_index,
+                                   unsigned long *words, const uint64_t *word_offsets,
+                                   const uint32_t *block_counts, uint64_t n_rec, unsigned flags, void *hip_stream);
+int BRB_Blowfish_DecryptBatchKeyed(const BRB_BLOWFISH_CTX *ctxs, uint64_t n_ctx, const uint32_t *ctx_index,
+                                   unsigned long *words, const uint64_t *word_offsets,
+                                   const uint32_t *block_counts, uint64_t n_rec, unsigned flags, void *hip_stream);
+
 /* ---- Key setup as a batch (EvAIOReqTransform_CryptoEnable, ev_kq_aio_transform.c:75-108) ------
  * Key i = keys[key_offsets[i] .. + key_lengths[i]).  Keys may sit at any byte offset and may overlap
  * or be shared: one key used by every record (all offsets equal) is the daemon's normal case.  Only
@@ -442,6 +468,30 @@ int BRB_MemBufferEncrypt(void *buf, unsigned long size, unsigned int seed, unsig
 int BRB_MemBufferDecrypt(void *buf, unsigned long size, unsigned int seed, unsigned long offset,
                          unsigned long *new_size, unsigned flags, void *hip_stream);
 
+/* The same for n_buf MemBuffers in one call (one key-setup launch for the seeds, one keyed ECB launch,
+ * one synchronisation).  Buffer i is data + buf_offsets[i]; its MemBuffer size is sizes[i], its offset
+ * argument offsets[i] (offsets == NULL: 0 for all), its seed seeds[seed_index ? seed_index[i] :
+ * (n_seeds == 1 ? 0 : i)].  Semantics per buffer exactly as the single calls (key derivation, keyLen 4
+ * / 64, the +2 words rounded up to pairs, the zero-word stop -- bytes from the stop onward are not
+ * written), new_sizes[i] as *new_size; the caller grows and zero-fills every buffer to BRB_MEMBUF_SPAN
+ * first, and the buffers' spans must not overlap.  seeds is always host memory (a parameter, not
+ * data); data and the other arrays follow flags.  n_seeds must be >= 1, and 1 or n_buf when seed_index
+ * is NULL (-1 otherwise).  Host mode: any byte alignment per buffer; a decrypt sizes[i] < offsets[i], a
+ * seed_index[i] >= n_seeds or a buffer of 2^32 pairs or more returns -1; on a refusal nothing is
+ * written; BRB_BATCH_ALL_DEVICES is accepted and runs on the calling thread's device.  Device mode:
+ * data must be 8-byte aligned (-1 otherwise) and so must every buf_offsets[i] + offsets[i], the
+ * caller's promise; a buffer that breaks that promise or one of the host-mode rules above is left
+ * untouched (its new_sizes[i] is then meaningless).  The contexts live in the calling thread's
+ * workspace, so both modes return when new_sizes is known (ASYNC is ignored).  n_buf == 0 returns 1. */
+int BRB_MemBufferEncryptBatch(void *data, const uint64_t *buf_offsets, const uint64_t *sizes,
+                              const uint64_t *offsets, const unsigned int *seeds, uint64_t n_seeds,
+                              const uint32_t *seed_index, uint64_t n_buf, uint64_t *new_sizes, unsigned flags,
+                              void *hip_stream);
+int BRB_MemBufferDecryptBatch(void *data, const uint64_t *buf_offsets, const uint64_t *sizes,
+                              const uint64_t *offsets, const unsigned int *seeds, uint64_t n_seeds,
+                              const uint32_t *seed_index, uint64_t n_buf, uint64_t *new_sizes, unsigned flags,
+                              void *hip_stream);
+
 /* ---- runtime ---------------------------------------------------------------------------- */
 /* 1 if a HIP device is usable from this process, else 0 (reason in LastError). */
 int BRB_CryptoGPU_Available(void);
@@ -487,7 +537,9 @@ int BRB_CryptoGPU_HostUnregister(void *p);
  * partner wave pairs / one wave per connection), "rc4_pair" 1/0 (BRB_RC4_CryptBatch likewise; a forced
  * "rc4_sector" value selects the one-wave kernel), "pair_stall" 0/1 (1: the segment, MetaData, RC4
  * pass and RC4+MD5 frame / open wave pairs get a protocol fault injected, so the call returns
- * BRB_BATCH_FAULT, an async call's check reports it and a batcher round is dropped).  Returns 1 and the previous
+ * BRB_BATCH_FAULT, an async call's check reports it and a batcher round is dropped), "bf_keyed" 0/1/2
+ * (the keyed Blowfish ECB calls: spread image fill and two blocks per lane / the plain fill / one
+ * block per lane).  Returns 1 and the previous
  * value in *old (if not NULL), or -1 for an unknown name or a value out of range. */
 int BRB_CryptoGPU_TestOption(const char *name, int value, int *old);
 /* Library version string. */
