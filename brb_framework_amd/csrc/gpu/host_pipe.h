@@ -1,4 +1,6 @@
-// host_pipe.h -- host-mode execution of the batch calls (internal, not exported).
+// host_pipe.h -- host-mode execution of the fixed-stride batch calls and the all-devices split
+// (internal, not exported).  Implemented in host_pipe.hip and called by the entry points in
+// batch_api.hip; the workspace it stages in is the per-thread runtime's (api_util.h, api_runtime.hip).
 //
 // A host-mode call starts and ends in the caller's host memory (the kqueue receive path's socket
 // buffers, mem_buf.c:1224-1254 recv() into a calloc'd MemBuffer), so it is bound by PCIe, not HBM.
@@ -14,11 +16,6 @@
 #include <functional>
 
 #include "brb_crypto.h"
-
-namespace brb_api {
-// Per-thread, per-device grow-only device scratch (batch_api.hip).
-void *workspace(size_t bytes, hipError_t *err);
-}  // namespace brb_api
 
 namespace brb_host {
 

@@ -27,11 +27,10 @@
 
 namespace {
 
+using brb_api::align_up;
 using brb_api::DeviceGuard;
 using brb_api::fail_hip;
 using brb_api::set_err;
-
-inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
 // Input bytes per chunk.  Every pageable chunk copy pays a fixed cost (8 MiB pieces copy at
 // 52 GB/s, one 98 MB copy at 56.5 GB/s), while only the first chunk's H2D and the last chunk's D2H
@@ -225,12 +224,19 @@ int drain(Pipe *p, int rc)
     return rc;
 }
 
-// One device's share of a fixed-stride digest batch: H2D chunk by chunk on s_in (calling thread),
-// one kernel per chunk on s_k once its bytes have landed, and each chunk's digests back through the
-// device's D2H worker while later chunks are still going up (cfg3's 64-byte records return a
-// quarter of their bytes as digests).
-int digest_part(brb_host::FixedLauncher launch, size_t dig, const uint8_t *data, uint32_t L, uint64_t n,
-                uint8_t *digests)
+// One device's share of a host-mode batch of n items, cut into chunks of `per` items, in `ws_bytes`
+// of the thread's workspace `ws`.  Chunk [i, i + m): up(ws, i, m, stream) copies its inputs H2D on
+// s_in (calling thread), launch(ws, i, m, stream) runs on s_k once they have landed (both return a
+// hipError_t), and the range down(ws, i, m) names comes back through the device's D2H worker on s_out
+// while later chunks are still going up.
+struct D2H {
+    void *dst;
+    const void *src;
+    size_t bytes;
+};
+
+template <class Up, class Launch, class Down>
+int chunked(size_t ws_bytes, uint64_t n, uint64_t per, Up up, Launch launch, Down down)
 {
     hipError_t e;
     int dev = 0;
@@ -239,20 +245,19 @@ int digest_part(brb_host::FixedLauncher launch, size_t dig, const uint8_t *data,
     Pipe *p = pipe_for(dev, &e);
     if (!p)
         return fail_hip("host pipeline streams", e);
-    const size_t in_bytes = size_t(L) * n, off_out = align_up(in_bytes, 256);
-    uint8_t *ws = static_cast<uint8_t *>(brb_api::workspace(off_out + dig * n, &e));
+    uint8_t *ws = static_cast<uint8_t *>(brb_api::workspace(ws_bytes, &e));
     if (!ws)
         return fail_hip("device workspace", e);
-    const uint64_t per = L ? std::max<uint64_t>(1, digest_chunk_bytes() / L) : n;
     if (per >= n) {
         // one chunk: nothing to overlap, so no worker hand-off and no events -- H2D, kernel and D2H
         // in order on one stream (tools/call_latency.cpp: the pipeline's machinery cost ~48 us per
         // call on batches of 1..1024 records)
-        if (L && (e = hipMemcpyAsync(ws, data, n * L, hipMemcpyHostToDevice, p->s_k)) != hipSuccess)
+        const D2H d = down(ws, 0, n);
+        if ((e = up(ws, 0, n, p->s_k)) != hipSuccess)
             return drain(p, fail_hip("hipMemcpyAsync H2D", e));
-        if ((e = launch(ws, L, n, ws + off_out, p->s_k)) != hipSuccess)
+        if ((e = launch(ws, 0, n, p->s_k)) != hipSuccess)
             return drain(p, fail_hip("kernel launch", e));
-        if ((e = hipMemcpyAsync(digests, ws + off_out, dig * n, hipMemcpyDeviceToHost, p->s_k)) != hipSuccess)
+        if ((e = hipMemcpyAsync(d.dst, d.src, d.bytes, hipMemcpyDeviceToHost, p->s_k)) != hipSuccess)
             return drain(p, fail_hip("hipMemcpyAsync D2H", e));
         if ((e = hipStreamSynchronize(p->s_k)) != hipSuccess)
             return drain(p, fail_hip("hipStreamSynchronize", e));
@@ -264,16 +269,18 @@ int digest_part(brb_host::FixedLauncher launch, size_t dig, const uint8_t *data,
     for (uint64_t i = 0; i < n && rc == BRB_BATCH_OK && !pending.failed(); i += per, c++) {
         const uint64_t m = std::min(per, n - i);
         hipEvent_t ev_in = p->ev_in[c % kEvents], ev_k = p->ev_k[c % kEvents];
-        if (L && (e = hipMemcpyAsync(ws + i * L, data + i * L, m * L, hipMemcpyHostToDevice, p->s_in)) != hipSuccess)
+        if ((e = up(ws, i, m, p->s_in)) != hipSuccess)
             rc = fail_hip("hipMemcpyAsync H2D", e);
         else if ((e = hipEventRecord(ev_in, p->s_in)) != hipSuccess || (e = hipStreamWaitEvent(p->s_k, ev_in, 0)) != hipSuccess)
             rc = fail_hip("chunk event", e);
-        else if ((e = launch(ws + i * L, L, m, ws + off_out + i * dig, p->s_k)) != hipSuccess)
+        else if ((e = launch(ws, i, m, p->s_k)) != hipSuccess)
             rc = fail_hip("kernel launch", e);
         else if ((e = hipEventRecord(ev_k, p->s_k)) != hipSuccess)
             rc = fail_hip("chunk event", e);
-        else
-            post_d2h(dev, pending, p->s_out, ev_k, digests + i * dig, ws + off_out + i * dig, dig * m);
+        else {
+            const D2H d = down(ws, i, m);
+            post_d2h(dev, pending, p->s_out, ev_k, d.dst, d.src, d.bytes);
+        }
     }
     std::string why;
     const int rc_out = pending.wait(&why);
@@ -284,60 +291,38 @@ int digest_part(brb_host::FixedLauncher launch, size_t dig, const uint8_t *data,
     return drain(p, rc);
 }
 
-// One device's share of a Blowfish batch: the words go up chunk by chunk on s_in (calling thread),
-// each chunk is enciphered on s_k, and the device's D2H worker brings it back on s_out while later
-// chunks are still going up.
+// Fixed-stride digests: a chunk's records go up, and its digests come back (cfg3's 64-byte records
+// return a quarter of their bytes as digests).
+int digest_part(brb_host::FixedLauncher launch, size_t dig, const uint8_t *data, uint32_t L, uint64_t n,
+                uint8_t *digests)
+{
+    const size_t off_out = align_up(size_t(L) * n, 256);
+    const uint64_t per = L ? std::max<uint64_t>(1, digest_chunk_bytes() / L) : n;
+    return chunked(
+        off_out + dig * n, n, per,
+        [&](uint8_t *ws, uint64_t i, uint64_t m, hipStream_t s) {
+            return L ? hipMemcpyAsync(ws + i * L, data + i * L, m * L, hipMemcpyHostToDevice, s) : hipSuccess;
+        },
+        [&](uint8_t *ws, uint64_t i, uint64_t m, hipStream_t s) { return launch(ws + i * L, L, m, ws + off_out + i * dig, s); },
+        [&](uint8_t *ws, uint64_t i, uint64_t m) { return D2H{digests + i * dig, ws + off_out + i * dig, dig * m}; });
+}
+
+// Blowfish ECB in place: a chunk's words go up, are enciphered and come back.  The context goes up
+// once, ahead of the first chunk on the same stream.
 int blowfish_part(const BRB_BLOWFISH_CTX *ctx, uint64_t *words, uint64_t nb, bool decrypt)
 {
-    hipError_t e;
-    int dev = 0;
-    if ((e = hipGetDevice(&dev)) != hipSuccess)
-        return fail_hip("hipGetDevice", e);
-    Pipe *p = pipe_for(dev, &e);
-    if (!p)
-        return fail_hip("host pipeline streams", e);
     const size_t ctx_bytes = align_up(sizeof(BRB_BLOWFISH_CTX), 256);
-    uint8_t *ws = static_cast<uint8_t *>(brb_api::workspace(ctx_bytes + 16 * size_t(nb), &e));
-    if (!ws)
-        return fail_hip("device workspace", e);
-    const uint64_t *dctx = reinterpret_cast<const uint64_t *>(ws);
-    uint64_t *dw = reinterpret_cast<uint64_t *>(ws + ctx_bytes);
-    const uint64_t per = std::max<uint64_t>(1, chunk_bytes() / 16);
-    if (per >= nb) {                                           // one chunk: one stream, one sync
-        if ((e = hipMemcpyAsync(ws, ctx, sizeof(BRB_BLOWFISH_CTX), hipMemcpyHostToDevice, p->s_k)) != hipSuccess ||
-            (e = hipMemcpyAsync(dw, words, 16 * nb, hipMemcpyHostToDevice, p->s_k)) != hipSuccess ||
-            (e = brb::launch_blowfish(dctx, dw, nb, decrypt, p->s_k)) != hipSuccess ||
-            (e = hipMemcpyAsync(words, dw, 16 * nb, hipMemcpyDeviceToHost, p->s_k)) != hipSuccess ||
-            (e = hipStreamSynchronize(p->s_k)) != hipSuccess)
-            return drain(p, fail_hip("single-chunk Blowfish batch", e));
-        return BRB_BATCH_OK;
-    }
-    if ((e = hipMemcpyAsync(ws, ctx, sizeof(BRB_BLOWFISH_CTX), hipMemcpyHostToDevice, p->s_in)) != hipSuccess)
-        return drain(p, fail_hip("hipMemcpyAsync H2D", e));
-    Pending pending;
-    int rc = BRB_BATCH_OK;
-    uint64_t c = 0;
-    for (uint64_t i = 0; i < nb && rc == BRB_BATCH_OK && !pending.failed(); i += per, c++) {
-        const uint64_t m = std::min(per, nb - i);
-        hipEvent_t ev_in = p->ev_in[c % kEvents], ev_k = p->ev_k[c % kEvents];
-        if ((e = hipMemcpyAsync(dw + 2 * i, words + 2 * i, 16 * m, hipMemcpyHostToDevice, p->s_in)) != hipSuccess)
-            rc = fail_hip("hipMemcpyAsync H2D", e);
-        else if ((e = hipEventRecord(ev_in, p->s_in)) != hipSuccess || (e = hipStreamWaitEvent(p->s_k, ev_in, 0)) != hipSuccess)
-            rc = fail_hip("chunk event", e);
-        else if ((e = brb::launch_blowfish(dctx, dw + 2 * i, m, decrypt, p->s_k)) != hipSuccess)
-            rc = fail_hip("kernel launch", e);
-        else if ((e = hipEventRecord(ev_k, p->s_k)) != hipSuccess)
-            rc = fail_hip("chunk event", e);
-        else
-            post_d2h(dev, pending, p->s_out, ev_k, words + 2 * i, dw + 2 * i, 16 * m);
-    }
-    std::string why;
-    const int rc_out = pending.wait(&why);
-    if (rc == BRB_BATCH_OK && rc_out != BRB_BATCH_OK) {
-        brb_api::t_err = why;
-        rc = rc_out;
-    }
-    return drain(p, rc);
+    auto dw = [&](uint8_t *ws, uint64_t i) { return reinterpret_cast<uint64_t *>(ws + ctx_bytes) + 2 * i; };
+    return chunked(
+        ctx_bytes + 16 * size_t(nb), nb, std::max<uint64_t>(1, chunk_bytes() / 16),
+        [&](uint8_t *ws, uint64_t i, uint64_t m, hipStream_t s) {
+            const hipError_t e = i ? hipSuccess : hipMemcpyAsync(ws, ctx, sizeof(BRB_BLOWFISH_CTX), hipMemcpyHostToDevice, s);
+            return e != hipSuccess ? e : hipMemcpyAsync(dw(ws, i), words + 2 * i, 16 * m, hipMemcpyHostToDevice, s);
+        },
+        [&](uint8_t *ws, uint64_t i, uint64_t m, hipStream_t s) {
+            return brb::launch_blowfish(reinterpret_cast<const uint64_t *>(ws), dw(ws, i), m, decrypt, s);
+        },
+        [&](uint8_t *ws, uint64_t i, uint64_t m) { return D2H{words + 2 * i, dw(ws, i), 16 * m}; });
 }
 
 }  // namespace

@@ -8,7 +8,7 @@
 // waves carry no fault code, so their loops compile as before.  A fault word is 32 bits of
 // page-locked, device-mapped, portable host memory, and the launchers pass whichever word is armed
 // on the launching thread:
-//   * a synchronous batch call arms the thread's call word (PairFault in batch_api.hip: one
+//   * a synchronous batch call arms the thread's call word (PairFault, api_util.h / api_runtime.hip: one
 //     thread-local store, nothing between the caller and the launch) and reads it once the stream
 //     has drained: a set word turns the call into BRB_BATCH_FAULT (-4) with "wave-pair protocol
 //     fault" in BRB_CryptoGPU_LastError();

@@ -1,5 +1,5 @@
 // test_options.h -- process-wide A/B and test switches, set only through the exported test-support
-// call BRB_CryptoGPU_TestOption (batch_api.hip).  The library reads no environment variable: a
+// call BRB_CryptoGPU_TestOption (api_runtime.hip).  The library reads no environment variable: a
 // stray variable in a production process cannot change a code path.
 #pragma once
 
