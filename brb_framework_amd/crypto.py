@@ -98,6 +98,22 @@ _SIGNATURES = [
     ("BrbSha1_Batch", ctypes.c_int,
      [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint,
       ctypes.c_void_p]),
+    ("BRB_MD5InitBatch", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint, ctypes.c_void_p]),
+    ("BRB_MD5UpdateBatch", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+      ctypes.c_uint64, ctypes.c_uint, ctypes.c_void_p]),
+    ("BRB_MD5FinalBatch", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint,
+      ctypes.c_void_p]),
+    ("BrbSha1_InitBatch", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint, ctypes.c_void_p]),
+    ("BrbSha1_UpdateBatch", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+      ctypes.c_uint64, ctypes.c_uint, ctypes.c_void_p]),
+    ("BrbSha1_FinalBatch", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint,
+      ctypes.c_void_p]),
     ("BRB_Blowfish_EncryptBatch", ctypes.c_int,
      [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint, ctypes.c_void_p]),
     ("BRB_Blowfish_DecryptBatch", ctypes.c_int,
@@ -386,6 +402,134 @@ def metadata_pack_batch(data, item_offsets, item_lengths, item_ids, item_sub_ids
 
 def sha1_batch(data, offsets, lengths, out=None, stream=None, async_=False, all_devices=False):
     return _digest_var(lib().BrbSha1_Batch, 20, data, offsets, lengths, out, stream, async_, all_devices)
+
+
+# ---- streaming MD5 / SHA-1 contexts as a batch ----------------------------------------------------
+MD5_CTX_BYTES = 168
+SHA1_CTX_BYTES = 92
+
+
+def _ctx_row(row, ctype):
+    """A pointer to the compat struct held in one row of a host context table."""
+    if not (isinstance(row, np.ndarray) and row.dtype == np.uint8 and row.flags["C_CONTIGUOUS"]
+            and row.nbytes == ctypes.sizeof(ctype)):
+        raise ValueError(f"a context row is a contiguous uint8 array of {ctypes.sizeof(ctype)} bytes")
+    return ctypes.cast(row.ctypes.data, ctypes.POINTER(ctype))
+
+
+def md5_ctx_init(row) -> None:
+    """BRB_MD5Init (host, compat) on one row of a (n_ctx, 168) table."""
+    lib().BRB_MD5Init(_ctx_row(row, BRB_MD5_CTX))
+
+
+def md5_ctx_update(row, piece) -> None:
+    """BRB_MD5Update (host, compat) of one row with `piece` (bytes)."""
+    piece = bytes(piece)
+    lib().BRB_MD5Update(_ctx_row(row, BRB_MD5_CTX), ctypes.create_string_buffer(piece, max(len(piece), 1)), len(piece))
+
+
+def md5_ctx_final(row) -> bytes:
+    """BRB_MD5Final (host, compat) of one row; returns the 16 digest bytes."""
+    lib().BRB_MD5Final(_ctx_row(row, BRB_MD5_CTX))
+    return row[88:104].tobytes()
+
+
+def sha1_ctx_init(row) -> None:
+    """BrbSha1_Init (host, compat) on one row of a (n_ctx, 92) table."""
+    lib().BrbSha1_Init(_ctx_row(row, BrbSha1Ctx))
+
+
+def sha1_ctx_update(row, piece) -> None:
+    """BrbSha1_Update (host, compat) of one row with a private copy of `piece` (the call rewrites its input)."""
+    piece = bytes(piece)
+    lib().BrbSha1_Update(_ctx_row(row, BrbSha1Ctx), ctypes.create_string_buffer(piece, max(len(piece), 1)), len(piece))
+
+
+def sha1_ctx_final(row) -> bytes:
+    """BrbSha1_Final (host, compat) of one row (zeroed afterwards); returns the 20 digest bytes."""
+    out = ctypes.create_string_buffer(20)
+    lib().BrbSha1_Final(_ctx_row(row, BrbSha1Ctx), out)
+    return out.raw
+
+
+def _stream_n(ctxs, width, ctx_index, n):
+    """(n_ctx, n) of a context-table call: n defaults to len(ctx_index), or to the whole table."""
+    if _nbytes(ctxs) % width:
+        raise ValueError(f"ctxs holds {_nbytes(ctxs)} bytes, not a multiple of {width}")
+    n_ctx = _nbytes(ctxs) // width
+    if ctx_index is not None:
+        if n is not None and n != len(ctx_index):
+            raise ValueError("n differs from len(ctx_index)")
+        return n_ctx, len(ctx_index)
+    return n_ctx, n_ctx if n is None else n
+
+
+def _stream_init(fn, width, ctxs, ctx_index, n, stream, async_, all_devices):
+    _same_kind(ctxs, ctx_index)
+    n_ctx, n = _stream_n(ctxs, width, ctx_index, n)
+    flags, h = _mode(ctxs, stream, async_, all_devices)
+    _check(fn(_ptr(ctxs), n_ctx, _ptr(ctx_index), n, flags, h), fn.__name__)
+    return ctxs
+
+
+def _stream_update(fn, width, ctxs, data, offsets, lengths, ctx_index, stream, async_, all_devices):
+    _same_kind(ctxs, data, offsets, lengths, ctx_index)
+    n_ctx, n = _stream_n(ctxs, width, ctx_index, len(offsets))
+    if len(lengths) != n:
+        raise ValueError("offsets, lengths and ctx_index differ in length")
+    flags, h = _mode(ctxs, stream, async_, all_devices)
+    _check(fn(_ptr(ctxs), n_ctx, _ptr(ctx_index), _ptr(data), _ptr(offsets), _ptr(lengths), n, flags, h), fn.__name__)
+    return ctxs
+
+
+def _stream_final(fn, width, dig, ctxs, ctx_index, n, out, stream, async_, all_devices):
+    _same_kind(ctxs, ctx_index, out)
+    n_ctx, n = _stream_n(ctxs, width, ctx_index, n)
+    if out is None:
+        out = _out_like(ctxs, n, dig)
+    elif _nbytes(out) < n * dig:
+        raise ValueError(f"out holds {_nbytes(out)} bytes, {n} digests need {n * dig}")
+    flags, h = _mode(ctxs, stream, async_, all_devices)
+    _check(fn(_ptr(ctxs), n_ctx, _ptr(ctx_index), n, _ptr(out), flags, h), fn.__name__)
+    return out
+
+
+def md5_init_batch(ctxs, ctx_index=None, n=None, stream=None, async_=False, all_devices=False):
+    """BRB_MD5InitBatch: BRB_MD5Init of ctxs[ctx_index[i]] (ctx_index None: the first n contexts, all by
+    default).  ctxs: (n_ctx, 168) uint8, numpy for host mode or a CUDA tensor for device mode (ctx_index
+    uint32[n] / an int32 tensor of the same kind); updated in place and returned."""
+    return _stream_init(lib().BRB_MD5InitBatch, MD5_CTX_BYTES, ctxs, ctx_index, n, stream, async_, all_devices)
+
+
+def md5_update_batch(ctxs, data, offsets, lengths, ctx_index=None, stream=None, async_=False, all_devices=False):
+    """BRB_MD5UpdateBatch: context ctx_index[i] (None: i) takes the piece data[offsets[i]:+lengths[i]], as
+    BRB_MD5Update would.  A context may be named once per call.  offsets uint64[n], lengths uint32[n]."""
+    return _stream_update(lib().BRB_MD5UpdateBatch, MD5_CTX_BYTES, ctxs, data, offsets, lengths, ctx_index, stream,
+                          async_, all_devices)
+
+
+def md5_final_batch(ctxs, ctx_index=None, n=None, out=None, stream=None, async_=False, all_devices=False):
+    """BRB_MD5FinalBatch: BRB_MD5Final of the named contexts (buf, digest, hex string); returns the
+    digests (n, 16) in item order."""
+    return _stream_final(lib().BRB_MD5FinalBatch, MD5_CTX_BYTES, 16, ctxs, ctx_index, n, out, stream, async_,
+                         all_devices)
+
+
+def sha1_init_batch(ctxs, ctx_index=None, n=None, stream=None, async_=False, all_devices=False):
+    """BrbSha1_InitBatch (see md5_init_batch); ctxs: (n_ctx, 92) uint8."""
+    return _stream_init(lib().BrbSha1_InitBatch, SHA1_CTX_BYTES, ctxs, ctx_index, n, stream, async_, all_devices)
+
+
+def sha1_update_batch(ctxs, data, offsets, lengths, ctx_index=None, stream=None, async_=False, all_devices=False):
+    """BrbSha1_UpdateBatch (see md5_update_batch); never writes into data."""
+    return _stream_update(lib().BrbSha1_UpdateBatch, SHA1_CTX_BYTES, ctxs, data, offsets, lengths, ctx_index, stream,
+                          async_, all_devices)
+
+
+def sha1_final_batch(ctxs, ctx_index=None, n=None, out=None, stream=None, async_=False, all_devices=False):
+    """BrbSha1_FinalBatch: returns the digests (n, 20); the named contexts are zeroed."""
+    return _stream_final(lib().BrbSha1_FinalBatch, SHA1_CTX_BYTES, 20, ctxs, ctx_index, n, out, stream, async_,
+                         all_devices)
 
 
 # ---- Blowfish ------------------------------------------------------------------------------------

@@ -299,6 +299,98 @@ int digest_var(VarLauncher launch, size_t dig_len, const void *data, const uint6
     });
 }
 
+// ---- streaming digest contexts as a batch (digest_stream_kernels.hip) --------------------------
+// BRB_MD5{Init,Update,Final}Batch and the BrbSha1_ three.  Item i acts on ctxs[ctx_index ? ctx_index[i] : i].
+// Host mode checks the index list before anything runs, stages only the named contexts (gathered in
+// item order, so the kernel runs without an index, and scattered back after it) and, for Update, the
+// pieces' span.  No wave-pair kernel: no fault word.
+enum StreamOp { kStreamInit, kStreamUpdate, kStreamFinal };
+
+int digest_stream(bool sha1, StreamOp op, void *ctxs, uint64_t n_ctx, const uint32_t *ctx_index, const void *data,
+                  const uint64_t *offsets, const uint32_t *lengths, uint64_t n, void *digests, unsigned flags, void *stream)
+{
+    t_err.clear();
+    if (n == 0)
+        return BRB_BATCH_OK;
+    if (!ctxs || (op == kStreamUpdate && (!offsets || !lengths)) || (op == kStreamFinal && sha1 && !digests)) {
+        set_err(op == kStreamUpdate ? "NULL ctxs, offsets or lengths" : op == kStreamFinal ? "NULL ctxs or digests" : "NULL ctxs");
+        return BRB_BATCH_BADARG;
+    }
+    if (!items_ok(n) || !flags_ok(flags))
+        return BRB_BATCH_BADARG;
+    const size_t stride = sha1 ? sizeof(BrbSha1Ctx) : sizeof(BRB_MD5_CTX), dig = sha1 ? 20 : 16;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    auto launch = [&](uint8_t *c, const uint32_t *ix, const uint8_t *d, const uint64_t *o, const uint32_t *l, uint8_t *dg) {
+        return op == kStreamInit     ? brb::launch_digest_stream_init(sha1, c, ix, n, s)
+               : op == kStreamUpdate ? brb::launch_digest_stream_update(sha1, c, ix, d, o, l, n, s)
+                                     : brb::launch_digest_stream_final(sha1, c, ix, n, dg, s);
+    };
+    if (flags & BRB_BATCH_DEVICE) {
+        if (int ok = device_ok(); ok != BRB_BATCH_OK)
+            return ok;
+        return device_run(launch(bytes(ctxs), ctx_index, bytes(data), offsets, lengths, bytes(digests)), s, flags);
+    }
+    // host mode: every list is host memory and is checked before anything runs
+    if (!ctx_index && n > n_ctx) {
+        set_err("ctx_index is NULL and n (%llu) > n_ctx (%llu)", (unsigned long long)n, (unsigned long long)n_ctx);
+        return BRB_BATCH_BADARG;
+    }
+    if (ctx_index) {
+        for (uint64_t i = 0; i < n; i++)
+            if (ctx_index[i] >= n_ctx) {
+                set_err("item %llu: ctx_index %u out of range (%llu contexts)", (unsigned long long)i, ctx_index[i],
+                        (unsigned long long)n_ctx);
+                return BRB_BATCH_BADARG;
+            }
+        std::vector<uint32_t> sorted(ctx_index, ctx_index + n);
+        std::sort(sorted.begin(), sorted.end());
+        const auto dup = std::adjacent_find(sorted.begin(), sorted.end());
+        if (dup != sorted.end()) {
+            set_err("context %u is named twice (two pieces of one chain in one call is a race)", *dup);
+            return BRB_BATCH_BADARG;
+        }
+    }
+    Span sp;
+    if (op == kStreamUpdate) {
+        sp = span_rebase(offsets, lengths, n);
+        if (!sp.ok)
+            return BRB_BATCH_BADARG;
+        if (!data && sp.bytes()) {
+            set_err("NULL data with a piece that has bytes");
+            return BRB_BATCH_BADARG;
+        }
+    }
+    if (int ok = device_ok(); ok != BRB_BATCH_OK)
+        return ok;
+    if (flags & BRB_BATCH_ALL_DEVICES)   // contiguous item ranges, one per device; the contexts go with their items
+        return brb_host::split_devices(n, [&](int, uint64_t lo, uint64_t hi) {
+            return digest_stream(sha1, op, ctx_index ? ctxs : bytes(ctxs) + lo * stride, ctx_index ? n_ctx : n_ctx - lo,
+                                 ctx_index ? ctx_index + lo : nullptr, data, offsets ? offsets + lo : nullptr,
+                                 lengths ? lengths + lo : nullptr, hi - lo, digests ? bytes(digests) + lo * dig : nullptr,
+                                 flags & ~BRB_BATCH_ALL_DEVICES, nullptr);
+        });
+    std::vector<uint8_t> named;                      // the named contexts in item order
+    if (ctx_index) {
+        named.resize(n * stride);
+        for (uint64_t i = 0; i < n; i++)
+            memcpy(named.data() + i * stride, bytes(ctxs) + ctx_index[i] * stride, stride);
+    }
+    Staging st;
+    const size_t i_c = st.inout(ctx_index ? named.data() : bytes(ctxs), n * stride);
+    const size_t i_d = op == kStreamUpdate ? st.in(data ? bytes(data) + sp.lo : nullptr, sp.bytes()) : 0;
+    const size_t i_o = op == kStreamUpdate ? st.in(sp.off.data(), 8 * n) : 0;
+    const size_t i_l = op == kStreamUpdate ? st.in(lengths, 4 * n) : 0;
+    const size_t i_g = op == kStreamFinal && digests ? st.out(digests, dig * n) : 0;
+    const int rc = st.run(s, nullptr, [&] {
+        return launched(launch(st.dev(i_c), nullptr, st.dev(i_d), st.dev<uint64_t>(i_o), st.dev<uint32_t>(i_l),
+                               op == kStreamFinal && digests ? st.dev(i_g) : nullptr));
+    });
+    if (rc == BRB_BATCH_OK && ctx_index)
+        for (uint64_t i = 0; i < n; i++)
+            memcpy(bytes(ctxs) + ctx_index[i] * stride, named.data() + i * stride, stride);
+    return rc;
+}
+
 int blowfish_batch(const BRB_BLOWFISH_CTX *ctx, unsigned long *words, uint64_t n_blocks, unsigned flags,
                    void *stream, bool decrypt)
 {
@@ -1032,6 +1124,42 @@ int BrbSha1_Batch(const void *data, const uint64_t *offsets, const uint32_t *len
                   uint8_t (*digests)[20], unsigned flags, void *hip_stream)
 {
     return digest_var(brb::launch_sha1_var, 20, data, offsets, lengths, n_rec, digests, flags, hip_stream);
+}
+
+int BRB_MD5InitBatch(BRB_MD5_CTX *ctxs, uint64_t n_ctx, const uint32_t *ctx_index, uint64_t n, unsigned flags,
+                     void *hip_stream)
+{
+    return digest_stream(false, kStreamInit, ctxs, n_ctx, ctx_index, nullptr, nullptr, nullptr, n, nullptr, flags, hip_stream);
+}
+
+int BRB_MD5UpdateBatch(BRB_MD5_CTX *ctxs, uint64_t n_ctx, const uint32_t *ctx_index, const void *data,
+                       const uint64_t *offsets, const uint32_t *lengths, uint64_t n, unsigned flags, void *hip_stream)
+{
+    return digest_stream(false, kStreamUpdate, ctxs, n_ctx, ctx_index, data, offsets, lengths, n, nullptr, flags, hip_stream);
+}
+
+int BRB_MD5FinalBatch(BRB_MD5_CTX *ctxs, uint64_t n_ctx, const uint32_t *ctx_index, uint64_t n,
+                      unsigned char (*digests)[16], unsigned flags, void *hip_stream)
+{
+    return digest_stream(false, kStreamFinal, ctxs, n_ctx, ctx_index, nullptr, nullptr, nullptr, n, digests, flags, hip_stream);
+}
+
+int BrbSha1_InitBatch(BrbSha1Ctx *ctxs, uint64_t n_ctx, const uint32_t *ctx_index, uint64_t n, unsigned flags,
+                      void *hip_stream)
+{
+    return digest_stream(true, kStreamInit, ctxs, n_ctx, ctx_index, nullptr, nullptr, nullptr, n, nullptr, flags, hip_stream);
+}
+
+int BrbSha1_UpdateBatch(BrbSha1Ctx *ctxs, uint64_t n_ctx, const uint32_t *ctx_index, const void *data,
+                        const uint64_t *offsets, const uint32_t *lengths, uint64_t n, unsigned flags, void *hip_stream)
+{
+    return digest_stream(true, kStreamUpdate, ctxs, n_ctx, ctx_index, data, offsets, lengths, n, nullptr, flags, hip_stream);
+}
+
+int BrbSha1_FinalBatch(BrbSha1Ctx *ctxs, uint64_t n_ctx, const uint32_t *ctx_index, uint64_t n, uint8_t (*digests)[20],
+                       unsigned flags, void *hip_stream)
+{
+    return digest_stream(true, kStreamFinal, ctxs, n_ctx, ctx_index, nullptr, nullptr, nullptr, n, digests, flags, hip_stream);
 }
 
 int BRB_Base64EncodeBatch(const void *data, const uint64_t *offsets, const uint32_t *lengths, uint64_t n, void *out,

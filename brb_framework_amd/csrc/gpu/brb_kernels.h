@@ -41,6 +41,15 @@ hipError_t launch_membuf_finish(const uint32_t *done, const uint64_t *offsets, u
 hipError_t launch_md5_segments(const uint8_t *data, const uint64_t *soff, const uint32_t *slen, const uint64_t *first,
                                uint64_t n_rec, uint8_t *out, hipStream_t s);
 
+// Streaming digest contexts (digest_stream_kernels.hip): item i acts on context ctx_index ? ctx_index[i] : i
+// of ctxs (BRB_MD5_CTX, 168 bytes; sha1: BrbSha1Ctx, 92 bytes; 4-byte aligned).  update: piece i =
+// data[offs[i] .. + lens[i]).  final: digests[i] (16 / 20 bytes, any alignment; MD5 only: may be nullptr).
+hipError_t launch_digest_stream_init(bool sha1, uint8_t *ctxs, const uint32_t *ctx_index, uint64_t n, hipStream_t s);
+hipError_t launch_digest_stream_update(bool sha1, uint8_t *ctxs, const uint32_t *ctx_index, const uint8_t *data,
+                                       const uint64_t *offs, const uint32_t *lens, uint64_t n, hipStream_t s);
+hipError_t launch_digest_stream_final(bool sha1, uint8_t *ctxs, const uint32_t *ctx_index, uint64_t n, uint8_t *digests,
+                                      hipStream_t s);
+
 // MetaDataUnpack of whole packs (metadata_kernels.hip): pack r = data[offs[r] .. + lens[r])
 hipError_t launch_metadata_unpack(const uint8_t *data, const uint64_t *offs, const uint32_t *lens, uint64_t n,
                                   BRB_MetaDataUnpackInfo *info, hipStream_t s);

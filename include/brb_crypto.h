@@ -232,6 +232,60 @@ int BrbSha1_BatchFixed(const void *data, uint32_t rec_len, uint64_t n_rec,
 int BrbSha1_Batch(const void *data, const uint64_t *offsets, const uint32_t *lengths,
                   uint64_t n_rec, uint8_t (*digests)[20], unsigned flags, void *hip_stream);
 
+/* ---- Streaming MD5 / SHA-1 contexts as a batch ------------------------------------------------
+ * The compat digests are streaming contexts (BRB_MD5Init / Update / UpdateBig / Final, BrbSha1_Init /
+ * Update / Final): a message arrives over several event-loop rounds, a file is digested in pieces.
+ * These calls keep a table of such contexts (n_ctx contiguous BRB_MD5_CTX of 168 bytes, or BrbSha1Ctx
+ * of 92 bytes) and act on n of them per call, one GPU lane per context, bit-compatible with the compat
+ * structs: a context may move freely between BRB_MD5Update / BrbSha1_Update on the host and these
+ * calls, and with BRB_BATCH_DEVICE the table lives in HBM across calls (as the RC4 states do).
+ *   Item i acts on ctxs[ctx_index ? ctx_index[i] : i].  A context may be named AT MOST ONCE per call:
+ *   two pieces of one chain in one launch is a race (a chain's pieces go in consecutive calls).
+ *   Piece i (Update) = data[offsets[i] .. + lengths[i]), at any byte alignment; pieces may overlap
+ *   each other; data is never written (unlike BrbSha1_Update, which rewrites its input blocks).
+ * Init writes exactly what BRB_MD5Init / BrbSha1_Init write -- the state words and the two counters --
+ *   and leaves every other byte of the struct as it was.
+ * Update leaves the DEFINED part of the context as BRB_MD5Update(&ctx, piece, len) (the same context as
+ *   BRB_MD5UpdateBig: one call for both) / BrbSha1_Update do.  The defined part is, for MD5, buf[4],
+ *   bytes[2] and the first bytes[0] & 63 bytes of in; for SHA-1, state[5], count[2] and the first
+ *   (count[0] >> 3) & 63 bytes of buffer.  The counters follow the reference's own arithmetic: MD5
+ *   carries from bytes[0] into bytes[1]; SHA-1 adds len << 3 to count[0], carries when the 32-bit sum is
+ *   below the untruncated len << 3 (the spurious carry of sha1.c:151 for len >= 2^29 included), then
+ *   adds len >> 29 to count[1].  Bytes of in / buffer PAST the buffered count are UNSPECIFIED after
+ *   Update (and MD5's in after Final): they may differ from what the compat call leaves there.  No later
+ *   call, host or batch, reads them before overwriting them.  MD5's digest and string are not touched.
+ *   A piece of length 0 changes nothing, and its offset need not be memory.
+ * MD5 Final = BRB_MD5Final: buf is the final state, digest its 16 bytes, string[0 .. 33) the lowercase
+ *   hex and its NUL; string[33 .. 64) and bytes are untouched; digests[i], when digests is not NULL,
+ *   gets the same 16 bytes, in item order.
+ * SHA-1 Final = BrbSha1_Final: 20 big-endian bytes to digests[i] (required), the whole context zeroed.
+ * Flags, return codes, hip_stream and the device-mode contract are BRB_MD5Batch's.  n == 0 returns 1.
+ * BRB_BATCH_DEVICE (optionally BRB_BATCH_ASYNC): ctxs, ctx_index, data, offsets, lengths and digests
+ * are device memory, ctxs 4-byte aligned; nothing is allocated (graph-capturable) and nothing is
+ * validated beyond NULL pointers and the item count.  BRB_BATCH_HOST returns -1 with a reason, and
+ * writes nothing, for: a NULL required pointer (ctx_index may be NULL; data may be NULL only when every
+ * length is 0; MD5's digests may be NULL); ctx_index[i] >= n_ctx; a NULL ctx_index with n > n_ctx; a
+ * context named twice; more items than a launch takes; BRB_BATCH_ALL_DEVICES with BRB_BATCH_DEVICE.
+ * Host mode stages only the contexts the items name (gathered in, scattered back: the rest of the
+ * table is neither read nor written) and the span of the pieces.  BRB_BATCH_ALL_DEVICES (host mode)
+ * splits the items into contiguous ranges, always: the contexts go with their items, and nothing is
+ * written back but contexts and digests.  No wave-pair kernel: BRB_BATCH_FAULT never occurs.  No CPU
+ * fallback: without a usable device the calls return 0 with a LastError and write nothing. */
+int BRB_MD5InitBatch(BRB_MD5_CTX *ctxs, uint64_t n_ctx, const uint32_t *ctx_index, uint64_t n,
+                     unsigned flags, void *hip_stream);
+int BRB_MD5UpdateBatch(BRB_MD5_CTX *ctxs, uint64_t n_ctx, const uint32_t *ctx_index,
+                       const void *data, const uint64_t *offsets, const uint32_t *lengths, uint64_t n,
+                       unsigned flags, void *hip_stream);
+int BRB_MD5FinalBatch(BRB_MD5_CTX *ctxs, uint64_t n_ctx, const uint32_t *ctx_index, uint64_t n,
+                      unsigned char (*digests)[16], unsigned flags, void *hip_stream);
+int BrbSha1_InitBatch(BrbSha1Ctx *ctxs, uint64_t n_ctx, const uint32_t *ctx_index, uint64_t n,
+                      unsigned flags, void *hip_stream);
+int BrbSha1_UpdateBatch(BrbSha1Ctx *ctxs, uint64_t n_ctx, const uint32_t *ctx_index,
+                        const void *data, const uint64_t *offsets, const uint32_t *lengths, uint64_t n,
+                        unsigned flags, void *hip_stream);
+int BrbSha1_FinalBatch(BrbSha1Ctx *ctxs, uint64_t n_ctx, const uint32_t *ctx_index, uint64_t n,
+                       uint8_t (*digests)[20], unsigned flags, void *hip_stream);
+
 /* Blowfish ECB over n_blocks blocks in place.  A block is the reference's (xl, xr) pair of
  * 64-bit `unsigned long` words (blowfish.c:312, mem_buf.c:1538-1539): words[2i] = xl,
  * words[2i+1] = xr.  The result equals BRB_Blowfish_Encrypt/Decrypt(ctx, &w[2i], &w[2i+1])
