@@ -114,6 +114,12 @@ _SIGNATURES = [
     ("BrbSha1_FinalBatch", ctypes.c_int,
      [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint,
       ctypes.c_void_p]),
+    ("BRB_MD5UpdateSegmentsBatch", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+      ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint, ctypes.c_void_p]),
+    ("BrbSha1_UpdateSegmentsBatch", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+      ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint, ctypes.c_void_p]),
     ("BRB_Blowfish_EncryptBatch", ctypes.c_int,
      [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint, ctypes.c_void_p]),
     ("BRB_Blowfish_DecryptBatch", ctypes.c_int,
@@ -492,6 +498,46 @@ def _stream_final(fn, width, dig, ctxs, ctx_index, n, out, stream, async_, all_d
     flags, h = _mode(ctxs, stream, async_, all_devices)
     _check(fn(_ptr(ctxs), n_ctx, _ptr(ctx_index), n, _ptr(out), flags, h), fn.__name__)
     return out
+
+
+def _stream_segments(fn, width, dig, ctxs, data, seg_offsets, seg_lengths, item_first_seg, final, ctx_index, out, stream,
+                     async_, all_devices):
+    _same_kind(ctxs, data, seg_offsets, seg_lengths, item_first_seg, final, ctx_index, out)
+    n_ctx, n = _stream_n(ctxs, width, ctx_index, len(item_first_seg) - 1)
+    if n < 0 or len(seg_offsets) != len(seg_lengths):
+        raise ValueError("item_first_seg needs n + 1 entries, and seg_offsets as many as seg_lengths")
+    if final is None:
+        out = None
+    else:
+        if len(final) != n or _nbytes(final) != n:
+            raise ValueError("final is one byte per item")
+        if out is None:
+            out = _out_like(ctxs, n, dig)
+            out[...] = 0                             # the rows of items that are not finalised are not written
+        elif _nbytes(out) < n * dig:
+            raise ValueError(f"out holds {_nbytes(out)} bytes, {n} digests need {n * dig}")
+    flags, h = _mode(ctxs, stream, async_, all_devices)
+    _check(fn(_ptr(ctxs), n_ctx, _ptr(ctx_index), _ptr(data), _ptr(seg_offsets), _ptr(seg_lengths), _ptr(item_first_seg),
+              n, _ptr(final), _ptr(out), flags, h), fn.__name__)
+    return out
+
+
+def md5_update_segments_batch(ctxs, data, seg_offsets, seg_lengths, item_first_seg, final=None, ctx_index=None, out=None,
+                              stream=None, async_=False, all_devices=False):
+    """BRB_MD5UpdateSegmentsBatch: context ctx_index[i] (None: i) takes the segments item_first_seg[i] ..
+    item_first_seg[i+1]-1 (n + 1 entries; segment k = data[seg_offsets[k]:+seg_lengths[k]]) in order, as one
+    BRB_MD5UpdateBig each, and is then finalised when final[i] != 0 (final: uint8[n], None: no item).  Returns
+    the digests (n, 16) -- only the rows of finalised items are written, the rest of a fresh `out` is 0 -- or
+    None when final is None."""
+    return _stream_segments(lib().BRB_MD5UpdateSegmentsBatch, MD5_CTX_BYTES, 16, ctxs, data, seg_offsets, seg_lengths,
+                            item_first_seg, final, ctx_index, out, stream, async_, all_devices)
+
+
+def sha1_update_segments_batch(ctxs, data, seg_offsets, seg_lengths, item_first_seg, final=None, ctx_index=None, out=None,
+                               stream=None, async_=False, all_devices=False):
+    """BrbSha1_UpdateSegmentsBatch (see md5_update_segments_batch): digests (n, 20); a finalised context is zeroed."""
+    return _stream_segments(lib().BrbSha1_UpdateSegmentsBatch, SHA1_CTX_BYTES, 20, ctxs, data, seg_offsets, seg_lengths,
+                            item_first_seg, final, ctx_index, out, stream, async_, all_devices)
 
 
 def md5_init_batch(ctxs, ctx_index=None, n=None, stream=None, async_=False, all_devices=False):

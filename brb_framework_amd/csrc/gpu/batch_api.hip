@@ -391,6 +391,104 @@ int digest_stream(bool sha1, StreamOp op, void *ctxs, uint64_t n_ctx, const uint
     return rc;
 }
 
+// BRB_MD5UpdateSegmentsBatch / BrbSha1_UpdateSegmentsBatch: item i advances ctxs[ctx_index ? ctx_index[i] : i] by
+// the segments first[i] .. first[i + 1] - 1 and is then finalised when fin && fin[i].  digest_stream's index checks
+// and context staging, BRB_MD5BatchSegments' segment staging; the digests are staged in both directions, so the rows
+// of items that are not finalised keep the caller's bytes.
+int digest_stream_segments(bool sha1, void *ctxs, uint64_t n_ctx, const uint32_t *ctx_index, const void *data,
+                           const uint64_t *soff, const uint32_t *slen, const uint64_t *first, uint64_t n,
+                           const uint8_t *fin, void *digests, unsigned flags, void *stream)
+{
+    t_err.clear();
+    if (n == 0)
+        return BRB_BATCH_OK;
+    if (!ctxs || !soff || !slen || !first || (sha1 && fin && !digests)) {
+        set_err("NULL ctxs, seg_offsets, seg_lengths, item_first_seg or digests");
+        return BRB_BATCH_BADARG;
+    }
+    if (!items_ok(n) || !flags_ok(flags))
+        return BRB_BATCH_BADARG;
+    const size_t stride = sha1 ? sizeof(BrbSha1Ctx) : sizeof(BRB_MD5_CTX), dig = sha1 ? 20 : 16;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (!fin)
+        digests = nullptr;                           // no item is finalised: not used
+    if (flags & BRB_BATCH_DEVICE) {
+        if (int ok = device_ok(); ok != BRB_BATCH_OK)
+            return ok;
+        return device_run(brb::launch_digest_stream_segments(sha1, bytes(ctxs), ctx_index, bytes(data), soff, slen, first, n,
+                                                             fin, bytes(digests), s),
+                          s, flags);
+    }
+    // host mode: every list is host memory and is checked before anything runs
+    if (!ctx_index && n > n_ctx) {
+        set_err("ctx_index is NULL and n (%llu) > n_ctx (%llu)", (unsigned long long)n, (unsigned long long)n_ctx);
+        return BRB_BATCH_BADARG;
+    }
+    if (ctx_index) {
+        for (uint64_t i = 0; i < n; i++)
+            if (ctx_index[i] >= n_ctx) {
+                set_err("item %llu: ctx_index %u out of range (%llu contexts)", (unsigned long long)i, ctx_index[i],
+                        (unsigned long long)n_ctx);
+                return BRB_BATCH_BADARG;
+            }
+        std::vector<uint32_t> sorted(ctx_index, ctx_index + n);
+        std::sort(sorted.begin(), sorted.end());
+        const auto dup = std::adjacent_find(sorted.begin(), sorted.end());
+        if (dup != sorted.end()) {
+            set_err("context %u is named twice (a chain's pieces of one call go in its segment list)", *dup);
+            return BRB_BATCH_BADARG;
+        }
+    }
+    for (uint64_t i = 0; i < n; i++)
+        if (first[i + 1] < first[i]) {
+            set_err("item_first_seg is not non-decreasing at %llu", (unsigned long long)i);
+            return BRB_BATCH_BADARG;
+        }
+    const uint64_t k0 = first[0], nseg = first[n] - k0;
+    const Span sp = span_rebase(soff + k0, slen + k0, nseg);
+    if (!sp.ok)
+        return BRB_BATCH_BADARG;
+    if (!data && sp.bytes()) {
+        set_err("NULL data with a segment that has bytes");
+        return BRB_BATCH_BADARG;
+    }
+    if (int ok = device_ok(); ok != BRB_BATCH_OK)
+        return ok;
+    if (flags & BRB_BATCH_ALL_DEVICES)   // contiguous item ranges, one per device; contexts and segment lists go with them
+        return brb_host::split_devices(n, [&](int, uint64_t lo, uint64_t hi) {
+            return digest_stream_segments(sha1, ctx_index ? ctxs : bytes(ctxs) + lo * stride, ctx_index ? n_ctx : n_ctx - lo,
+                                          ctx_index ? ctx_index + lo : nullptr, data, soff, slen, first + lo, hi - lo,
+                                          fin ? fin + lo : nullptr, digests ? bytes(digests) + lo * dig : nullptr,
+                                          flags & ~BRB_BATCH_ALL_DEVICES, nullptr);
+        });
+    std::vector<uint8_t> named;                      // the named contexts in item order
+    if (ctx_index) {
+        named.resize(n * stride);
+        for (uint64_t i = 0; i < n; i++)
+            memcpy(named.data() + i * stride, bytes(ctxs) + ctx_index[i] * stride, stride);
+    }
+    std::vector<uint64_t> rfirst(first, first + n + 1);
+    for (uint64_t &f : rfirst)
+        f -= k0;
+    Staging st;
+    const size_t i_c = st.inout(ctx_index ? named.data() : bytes(ctxs), n * stride);
+    const size_t i_d = st.in(data ? bytes(data) + sp.lo : nullptr, sp.bytes());
+    const size_t i_o = st.in(sp.off.data(), 8 * nseg);
+    const size_t i_l = st.in(slen + k0, 4 * nseg);
+    const size_t i_f = st.in(rfirst.data(), 8 * (n + 1));
+    const size_t i_n = fin ? st.in(fin, n) : 0;
+    const size_t i_g = digests ? st.inout(digests, dig * n) : 0;
+    const int rc = st.run(s, nullptr, [&] {
+        return launched(brb::launch_digest_stream_segments(sha1, st.dev(i_c), nullptr, st.dev(i_d), st.dev<uint64_t>(i_o),
+                                                           st.dev<uint32_t>(i_l), st.dev<uint64_t>(i_f), n,
+                                                           fin ? st.dev(i_n) : nullptr, digests ? st.dev(i_g) : nullptr, s));
+    });
+    if (rc == BRB_BATCH_OK && ctx_index)
+        for (uint64_t i = 0; i < n; i++)
+            memcpy(bytes(ctxs) + ctx_index[i] * stride, named.data() + i * stride, stride);
+    return rc;
+}
+
 int blowfish_batch(const BRB_BLOWFISH_CTX *ctx, unsigned long *words, uint64_t n_blocks, unsigned flags,
                    void *stream, bool decrypt)
 {
@@ -1160,6 +1258,23 @@ int BrbSha1_FinalBatch(BrbSha1Ctx *ctxs, uint64_t n_ctx, const uint32_t *ctx_ind
                        unsigned flags, void *hip_stream)
 {
     return digest_stream(true, kStreamFinal, ctxs, n_ctx, ctx_index, nullptr, nullptr, nullptr, n, digests, flags, hip_stream);
+}
+
+int BRB_MD5UpdateSegmentsBatch(BRB_MD5_CTX *ctxs, uint64_t n_ctx, const uint32_t *ctx_index, const void *data,
+                               const uint64_t *seg_offsets, const uint32_t *seg_lengths, const uint64_t *item_first_seg,
+                               uint64_t n, const uint8_t *final, unsigned char (*digests)[16], unsigned flags,
+                               void *hip_stream)
+{
+    return digest_stream_segments(false, ctxs, n_ctx, ctx_index, data, seg_offsets, seg_lengths, item_first_seg, n, final,
+                                  digests, flags, hip_stream);
+}
+
+int BrbSha1_UpdateSegmentsBatch(BrbSha1Ctx *ctxs, uint64_t n_ctx, const uint32_t *ctx_index, const void *data,
+                                const uint64_t *seg_offsets, const uint32_t *seg_lengths, const uint64_t *item_first_seg,
+                                uint64_t n, const uint8_t *final, uint8_t (*digests)[20], unsigned flags, void *hip_stream)
+{
+    return digest_stream_segments(true, ctxs, n_ctx, ctx_index, data, seg_offsets, seg_lengths, item_first_seg, n, final,
+                                  digests, flags, hip_stream);
 }
 
 int BRB_Base64EncodeBatch(const void *data, const uint64_t *offsets, const uint32_t *lengths, uint64_t n, void *out,

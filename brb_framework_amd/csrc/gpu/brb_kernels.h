@@ -49,6 +49,12 @@ hipError_t launch_digest_stream_update(bool sha1, uint8_t *ctxs, const uint32_t 
                                        const uint64_t *offs, const uint32_t *lens, uint64_t n, hipStream_t s);
 hipError_t launch_digest_stream_final(bool sha1, uint8_t *ctxs, const uint32_t *ctx_index, uint64_t n, uint8_t *digests,
                                       hipStream_t s);
+// segments: item i takes segments first[i] .. first[i + 1] - 1 (segment k = data[soff[k] .. + slen[k])) in order,
+// then Final when fin && fin[i] (digests[i] written for those items only; fin nullptr: no item is finalised).
+// Grid of ceil(n / 256); always this kernel, whatever the list lengths.
+hipError_t launch_digest_stream_segments(bool sha1, uint8_t *ctxs, const uint32_t *ctx_index, const uint8_t *data,
+                                         const uint64_t *soff, const uint32_t *slen, const uint64_t *first, uint64_t n,
+                                         const uint8_t *fin, uint8_t *digests, hipStream_t s);
 
 // MetaDataUnpack of whole packs (metadata_kernels.hip): pack r = data[offs[r] .. + lens[r])
 hipError_t launch_metadata_unpack(const uint8_t *data, const uint64_t *offs, const uint32_t *lens, uint64_t n,

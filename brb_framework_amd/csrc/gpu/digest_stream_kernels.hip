@@ -12,10 +12,15 @@
 // registers (four select stages).  The body is a plain BlockSrc over piece + room, its first block in
 // flight while the head is assembled and compressed: the loop of md5_any_kernel, started from the
 // context's state and ended without padding.  The last partial block goes to the context's buffer.
+//
+// Segments: item i advances its context by a LIST of segments and is then, optionally,
+// finalised -- Update, Final, the fused last piece and the whole-record segment digest in one kernel.
+// The bytes go through the lane's word funnel (stream_funnel.h), seeded from the context.
 #include "brb_kernels.h"
 #include "byte_stream.h"
 #include "md5_device.h"
 #include "sha1_device.h"
+#include "stream_funnel.h"
 
 namespace {
 
@@ -89,6 +94,12 @@ struct Md5Stream {                                  // BRB_MD5_CTX: buf[4], byte
         h[5] += h[4] < old ? 1u : 0u;
     }
     static BRB_DEV void compress(State &st, uint32_t (&w)[16]) { md5_compress(st, w); }
+    // final() leaves bytes as they are in memory: a call that advanced them before it stores them
+    static BRB_DEV void store_counts(uint8_t *cx, const uint32_t (&h)[kHdr])
+    {
+        stg(reinterpret_cast<uint32_t *>(cx + 16), h[4]);
+        stg(reinterpret_cast<uint32_t *>(cx + 20), h[5]);
+    }
 
     // w: the buffered bytes with the 0x80 marker, zeros behind it.  BRB_MD5Final (md5.c:134-168): buf,
     // digest and string[0 .. 33) are written; bytes, string[33 .. 64) and in are not.
@@ -147,6 +158,7 @@ struct Sha1Stream {                                 // BrbSha1Ctx: state[5], cou
             w[k] = __builtin_bswap32(w[k]);
         sha1_compress(st, w);
     }
+    static BRB_DEV void store_counts(uint8_t *, const uint32_t (&)[kHdr]) {}   // final() zeroes the context
 
     // BrbSha1_Final (sha1.c:171-195): the bit count is the counter pair as it stands, big-endian; the
     // digest is the state's words big-endian; the whole context is wiped.
@@ -278,6 +290,118 @@ __global__ __launch_bounds__(kBlock) void stream_final_kernel(uint8_t *ctxs, con
     A::final(cx, h, w, t, digests, i);
 }
 
+// Item i: the segments first[i] .. first[i + 1] - 1 into its context, in order, then Final when fin[i].
+// seg_lane's walk (md5_seg_kernels.hip) on a funnel seeded from the context: segment k is read in
+// 64-byte blocks as a range that starts e_k = (message bytes before it) mod 4 bytes early, so its words
+// fall on message word boundaries; those e bytes are the carried ones, never loaded from below the
+// segment.  The next non-empty segment's first block is in flight while the current one is hashed, and an
+// empty segment is skipped without forming an address.  The counters advance once per segment.
+template <class A>
+__global__ __launch_bounds__(kBlock) void stream_segments_kernel(uint8_t *ctxs, const uint32_t *__restrict__ ctx_index,
+                                                                 const uint8_t *__restrict__ data,
+                                                                 const uint64_t *__restrict__ soff,
+                                                                 const uint32_t *__restrict__ slen,
+                                                                 const uint64_t *__restrict__ first, uint64_t n,
+                                                                 const uint8_t *__restrict__ fin, uint8_t *digests)
+{
+    __shared__ __attribute__((aligned(8192))) uint32_t ring[kBlock / 64][brb_stream::kRingWords][64];   // 8 KiB per wave
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint64_t i = uint64_t(blockIdx.x) * kBlock + threadIdx.x;
+    if (i >= n)
+        return;
+    // The context is in flight while the lists are read, a segment's offset is loaded with its length, and
+    // the first segment's first block is started from the header alone, before the buffer is seeded.
+    const uint64_t k0 = first[i], k1 = first[i + 1];
+    const bool last = fin && fin[i];
+    uint8_t *cx = ctx_of<A>(ctxs, ctx_index, i);
+    uint32_t h[A::kHdr], in[16];
+    load_words(cx, h);
+    load_words(cx + 4 * A::kHdr, in);
+    // the next segment with bytes, its length and offset (an empty one's offset is read, never used)
+    auto find = [&](uint64_t kk, uint32_t &len, uint64_t &off) {
+        while (kk < k1) {
+            len = slen[kk];
+            off = soff[kk];
+            if (len)
+                break;
+            kk++;
+        }
+        return kk;
+    };
+    auto start = [&](brb_io::BlockSrc &src, uint64_t off, uint32_t len, uint32_t pre) {
+        const uint8_t *a = data + off;
+        const uint32_t e = pre & 3;
+        src.init(a - e, uint64_t(len) + e, a);
+    };
+    brb_io::BlockSrc sa, sb;
+    uint32_t la = 0, lb = 0;
+    uint64_t oa = 0, ob = 0;
+    uint64_t k = find(k0, la, oa);
+    if (k >= k1 && !last)                           // no bytes, no final: the context is not written
+        return;
+    const uint32_t have = A::have(h);
+    uint32_t before = have;                         // message bytes before the segment, mod 4
+    if (k < k1)
+        start(sa, oa, la, before);
+    brb_stream::Funnel<A> f;
+    f.seed(&ring[wave][0][lane], A::state(h), in, have);
+
+    auto run = [&](brb_io::BlockSrc &src, uint32_t len) {   // 64-byte blocks, the next one in flight
+        const uint64_t nb = uint64_t(len) + f.nacc;
+        for (uint64_t c = 0; c < nb; c += 64) {
+            uint32_t w[16];
+            src.fetch(w);
+            if (c == 0)
+                w[0] = f.head(w[0]);
+            const uint64_t left = nb - c;
+            bool direct = false;
+            if (left >= 64)
+                direct = f.put_block(w);
+            else
+                f.put_tail(w, uint32_t(left));
+            f.pump(w, direct);
+        }
+        if ((nb & 63) == 0) {                       // ended on a whole block: nothing carried
+            f.acc = 0;
+            f.nacc = 0;
+        }
+        A::advance(h, len);
+    };
+    while (k < k1) {
+        const uint64_t kb = find(k + 1, lb, ob);
+        if (kb < k1)
+            start(sb, ob, lb, before + la);
+        run(sa, la);
+        before += la;
+        if (kb >= k1)
+            break;
+        k = find(kb + 1, la, oa);               // sb's length is lb: la is free
+        if (k < k1)
+            start(sa, oa, la, before + lb);
+        run(sb, lb);
+        before += lb;
+    }
+
+    f.pump();                                       // fewer than 16 words pending
+    uint32_t w[16];
+    const uint32_t t = f.buffer(w);
+    A::put_state(h, f.st);
+    if (!last) {
+        uint32_t o[A::kHdr + 16];
+#pragma unroll
+        for (uint32_t j = 0; j < A::kHdr; j++)
+            o[j] = h[j];
+#pragma unroll
+        for (uint32_t j = 0; j < 16; j++)
+            o[A::kHdr + j] = w[j];
+        store_words(cx, o);                         // the context, once
+        return;
+    }
+    A::store_counts(cx, h);
+    brb_io::add_marker(w, t);
+    A::final(cx, h, w, t, digests, i);              // as stream_final_kernel
+}
+
 inline unsigned grid_for(uint64_t n)
 {
     return unsigned((n + kBlock - 1) / kBlock);
@@ -311,6 +435,17 @@ hipError_t launch_final(uint8_t *ctxs, const uint32_t *ctx_index, uint64_t n, ui
     return hipGetLastError();
 }
 
+template <class A>
+hipError_t launch_segments(uint8_t *ctxs, const uint32_t *ctx_index, const uint8_t *data, const uint64_t *soff,
+                           const uint32_t *slen, const uint64_t *first, uint64_t n, const uint8_t *fin, uint8_t *digests,
+                           hipStream_t s)
+{
+    if (n == 0)
+        return hipSuccess;
+    stream_segments_kernel<A><<<grid_for(n), kBlock, 0, s>>>(ctxs, ctx_index, data, soff, slen, first, n, fin, digests);
+    return hipGetLastError();
+}
+
 }  // namespace
 
 namespace brb {
@@ -332,6 +467,14 @@ hipError_t launch_digest_stream_final(bool sha1, uint8_t *ctxs, const uint32_t *
 {
     return sha1 ? launch_final<Sha1Stream>(ctxs, ctx_index, n, digests, s)
                 : launch_final<Md5Stream>(ctxs, ctx_index, n, digests, s);
+}
+
+hipError_t launch_digest_stream_segments(bool sha1, uint8_t *ctxs, const uint32_t *ctx_index, const uint8_t *data,
+                                         const uint64_t *soff, const uint32_t *slen, const uint64_t *first, uint64_t n,
+                                         const uint8_t *fin, uint8_t *digests, hipStream_t s)
+{
+    return sha1 ? launch_segments<Sha1Stream>(ctxs, ctx_index, data, soff, slen, first, n, fin, digests, s)
+                : launch_segments<Md5Stream>(ctxs, ctx_index, data, soff, slen, first, n, fin, digests, s);
 }
 
 }  // namespace brb

@@ -240,7 +240,8 @@ int BrbSha1_Batch(const void *data, const uint64_t *offsets, const uint32_t *len
  * structs: a context may move freely between BRB_MD5Update / BrbSha1_Update on the host and these
  * calls, and with BRB_BATCH_DEVICE the table lives in HBM across calls (as the RC4 states do).
  *   Item i acts on ctxs[ctx_index ? ctx_index[i] : i].  A context may be named AT MOST ONCE per call:
- *   two pieces of one chain in one launch is a race (a chain's pieces go in consecutive calls).
+ *   two pieces of one chain in one launch is a race (a chain's pieces go in consecutive calls, or as
+ *   one item's segment list in BRB_MD5UpdateSegmentsBatch / BrbSha1_UpdateSegmentsBatch below).
  *   Piece i (Update) = data[offsets[i] .. + lengths[i]), at any byte alignment; pieces may overlap
  *   each other; data is never written (unlike BrbSha1_Update, which rewrites its input blocks).
  * Init writes exactly what BRB_MD5Init / BrbSha1_Init write -- the state words and the two counters --
@@ -285,6 +286,50 @@ int BrbSha1_UpdateBatch(BrbSha1Ctx *ctxs, uint64_t n_ctx, const uint32_t *ctx_in
                         unsigned flags, void *hip_stream);
 int BrbSha1_FinalBatch(BrbSha1Ctx *ctxs, uint64_t n_ctx, const uint32_t *ctx_index, uint64_t n,
                        uint8_t (*digests)[20], unsigned flags, void *hip_stream);
+
+/* Segment lists per context and a fused Final: one call in which item i advances its context by a
+ * LIST of segments and is then, optionally, finalised.  One event-loop round delivers several buffers
+ * of one connection, a MetaData's items are scattered in memory (Init, one UpdateBig per item, Final),
+ * and in the same round some messages end while others go on: this call takes such a round in one
+ * launch, each context read and written once.  One segment and no final is UpdateBatch; no segments
+ * and final is FinalBatch; an Init'd context, segments and final is BRB_MD5BatchSegments.
+ *   Item i acts on ctxs[ctx_index ? ctx_index[i] : i]; a context is still named AT MOST ONCE per call.
+ *   Item i's segments are item_first_seg[i] .. item_first_seg[i + 1] - 1 (n + 1 entries, non-decreasing,
+ *   as rec_first_seg of BRB_MD5BatchSegments).  Segment k = data[seg_offsets[k] .. + seg_lengths[k]) at
+ *   any byte alignment; segments may overlap; data is never written; the offset of an empty segment
+ *   need not be memory.
+ * The result for item i is exactly what the compat functions leave after BRB_MD5UpdateBig (SHA-1:
+ *   BrbSha1_Update) once per segment, in order, and then, if final && final[i], BRB_MD5Final /
+ *   BrbSha1_Final -- "exactly" in the defined part that Update above documents: state, counters and the
+ *   buffered bytes; bytes of the block buffer past them stay unspecified.  The counters advance once
+ *   PER SEGMENT with the reference's own arithmetic, so SHA-1's spurious carry is per segment, as it is
+ *   per BrbSha1_Update call.
+ * An item with final[i] != 0.  MD5: buf, digest and string[0 .. 33) are as BRB_MD5Final leaves them,
+ *   bytes as the segments advanced it, string[33 .. 64) untouched; digests[i] is written when digests is
+ *   not NULL.  SHA-1: digests[i] is written (digests is required whenever final is not NULL) and the
+ *   whole context is zeroed.
+ * An item with final[i] == 0 leaves digests[i] untouched, in host mode too.  An item with no bytes (no
+ *   segments, or only empty ones) and no final leaves its context untouched.  final == NULL: no item is
+ *   finalised and digests is not used.  n == 0 returns 1.
+ * Flags, return codes, hip_stream and the device-mode contract are BRB_MD5UpdateBatch's.
+ * BRB_BATCH_DEVICE validates nothing beyond NULL pointers, the item count and the flags; ctxs is 4-byte
+ * aligned; nothing is allocated (graph-capturable).  BRB_BATCH_HOST returns -1 with a reason, and writes
+ * nothing, for: a NULL required pointer (data may be NULL only when every named segment is empty;
+ * ctx_index, final and MD5's digests may be NULL); ctx_index[i] >= n_ctx; a NULL ctx_index with
+ * n > n_ctx; a context named twice; item_first_seg that decreases; a segment range that wraps; more
+ * items than a launch takes; BRB_BATCH_ALL_DEVICES with BRB_BATCH_DEVICE.  Host mode stages the named
+ * contexts (gathered in, scattered back on success), the span of the named segments, and the digests in
+ * both directions.  BRB_BATCH_ALL_DEVICES splits the items into contiguous ranges, always; the contexts
+ * and the segment ranges go with their items.  No wave-pair kernel: BRB_BATCH_FAULT never occurs.  No
+ * CPU fallback: without a usable device the calls return 0 with a LastError and write nothing. */
+int BRB_MD5UpdateSegmentsBatch(BRB_MD5_CTX *ctxs, uint64_t n_ctx, const uint32_t *ctx_index,
+                               const void *data, const uint64_t *seg_offsets, const uint32_t *seg_lengths,
+                               const uint64_t *item_first_seg, uint64_t n, const uint8_t *final,
+                               unsigned char (*digests)[16], unsigned flags, void *hip_stream);
+int BrbSha1_UpdateSegmentsBatch(BrbSha1Ctx *ctxs, uint64_t n_ctx, const uint32_t *ctx_index,
+                                const void *data, const uint64_t *seg_offsets, const uint32_t *seg_lengths,
+                                const uint64_t *item_first_seg, uint64_t n, const uint8_t *final,
+                                uint8_t (*digests)[20], unsigned flags, void *hip_stream);
 
 /* Blowfish ECB over n_blocks blocks in place.  A block is the reference's (xl, xr) pair of
  * 64-bit `unsigned long` words (blowfish.c:312, mem_buf.c:1538-1539): words[2i] = xl,
