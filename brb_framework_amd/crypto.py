@@ -90,6 +90,10 @@ _SIGNATURES = [
     ("BRB_MetaDataUnpackBatch", ctypes.c_int,
      [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint,
       ctypes.c_void_p]),
+    ("BRB_MetaDataUnpackItemsBatch", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p,
+      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint,
+      ctypes.c_void_p]),
     ("BRB_MetaDataPackBatch", ctypes.c_int,
      [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
       ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint, ctypes.c_void_p]),
@@ -387,6 +391,42 @@ def metadata_unpack_batch(data, offsets, lengths, out=None, stream=None, async_=
     _check(lib().BRB_MetaDataUnpackBatch(_ptr(data), _ptr(offsets), _ptr(lengths), n, _ptr(out), flags, h),
            "BRB_MetaDataUnpackBatch")
     return out
+
+
+def metadata_unpack_items_batch(data, offsets, lengths, item_offsets, item_lengths, item_ids, item_sub_ids,
+                                pack_first_slot, items_added=None, out=None, stream=None, async_=False, all_devices=False):
+    """BRB_MetaDataUnpackItemsBatch: metadata_unpack_batch plus the item table.  Pack p's j-th MetaDataItemAdd
+    call (j below pack_first_slot[p + 1] - pack_first_slot[p]; n + 1 entries) is written to slot
+    pack_first_slot[p] + j of item_offsets (uint64: the data's offset in `data`), item_lengths (uint32),
+    item_ids and item_sub_ids (uint64); other slots keep their values.  numpy arrays in host mode, CUDA tensors
+    (int64 / int32) in device mode, all of one kind.  Returns (info, items_added): info as metadata_unpack_batch
+    returns it, items_added uint32[n] (an int32 tensor in device mode) = calls per pack, stored or not."""
+    _same_kind(data, offsets, lengths, item_offsets, item_lengths, item_ids, item_sub_ids, pack_first_slot, items_added,
+               out)
+    n = len(offsets)
+    if len(lengths) != n or len(pack_first_slot) != n + 1:
+        raise ValueError("lengths needs n entries and pack_first_slot n + 1")
+    if not (len(item_offsets) == len(item_lengths) == len(item_ids) == len(item_sub_ids)):
+        raise ValueError("the four item arrays differ in length")
+    if _is_torch(data):
+        import torch
+        if out is None:
+            out = torch.empty((n, METADATA_INFO_DTYPE.itemsize), dtype=torch.uint8, device=data.device)
+        if items_added is None:
+            items_added = torch.empty(n, dtype=torch.int32, device=data.device)
+    else:
+        if out is None:
+            out = np.empty(n, METADATA_INFO_DTYPE)
+        if items_added is None:
+            items_added = np.empty(n, np.uint32)
+        if n and int(pack_first_slot[n]) > len(item_offsets):
+            raise ValueError("pack_first_slot ends past the item arrays")
+    flags, h = _mode(data, stream, async_, all_devices)
+    _check(lib().BRB_MetaDataUnpackItemsBatch(_ptr(data), _ptr(offsets), _ptr(lengths), n, _ptr(out), _ptr(item_offsets),
+                                              _ptr(item_lengths), _ptr(item_ids), _ptr(item_sub_ids),
+                                              _ptr(pack_first_slot), _ptr(items_added), flags, h),
+           "BRB_MetaDataUnpackItemsBatch")
+    return out, items_added
 
 
 def metadata_pack_batch(data, item_offsets, item_lengths, item_ids, item_sub_ids, pack_first_item, out, out_offsets,

@@ -1122,6 +1122,72 @@ int BRB_MetaDataUnpackBatch(const void *data, const uint64_t *offs, const uint32
     });
 }
 
+// MetaDataUnpack with the item table.  Host mode stages the four item arrays over the slots the call
+// owns, [first[0], first[n]), in both directions -- slots no item reaches keep their values -- and
+// passes the staged span's base to the kernel, so item offsets are offsets in the caller's data.
+int BRB_MetaDataUnpackItemsBatch(const void *data, const uint64_t *offs, const uint32_t *lens, uint64_t n,
+                                 BRB_MetaDataUnpackInfo *info, uint64_t *ioff, uint32_t *ilen, uint64_t *iid,
+                                 uint64_t *isub, const uint64_t *first, uint32_t *added, unsigned flags, void *stream)
+{
+    t_err.clear();
+    if (n == 0)
+        return BRB_BATCH_OK;
+    if (!data || !offs || !lens || !info || !ioff || !ilen || !iid || !isub || !first || !added) {
+        set_err("NULL data, offsets, lengths, info, item_offsets, item_lengths, item_ids, item_sub_ids, pack_first_slot "
+                "or items_added");
+        return BRB_BATCH_BADARG;
+    }
+    if (!items_ok(n) || !flags_ok(flags))
+        return BRB_BATCH_BADARG;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (flags & BRB_BATCH_DEVICE) {
+        if (int ok = device_ok(); ok != BRB_BATCH_OK)
+            return ok;
+        const PairFault pf(flags);                   // pair_fault.h
+        return device_run(brb::launch_metadata_unpack_items(bytes(data), 0, offs, lens, n, info, ioff, ilen, iid, isub,
+                                                            first, added, s),
+                          s, flags, &pf);
+    }
+    // host mode: the slot list and the packs' span are host memory, so they are checked before anything runs
+    for (uint64_t p = 0; p < n; p++)
+        if (first[p + 1] < first[p]) {
+            set_err("pack_first_slot is not non-decreasing at %llu", (unsigned long long)p);
+            return BRB_BATCH_BADARG;
+        }
+    const Span sp = span_rebase(offs, lens, n);
+    if (!sp.ok)
+        return BRB_BATCH_BADARG;
+    if (int ok = device_ok(); ok != BRB_BATCH_OK)
+        return ok;
+    if (flags & BRB_BATCH_ALL_DEVICES)   // contiguous pack ranges, one per device; their slot ranges go with them
+        return brb_host::split_devices(n, [&](int, uint64_t lo, uint64_t hi) {
+            return BRB_MetaDataUnpackItemsBatch(data, offs + lo, lens + lo, hi - lo, info + lo, ioff, ilen, iid, isub,
+                                                first + lo, added + lo, flags & ~BRB_BATCH_ALL_DEVICES, nullptr);
+        });
+    const PairFault pf(flags);
+    const uint64_t k0 = first[0], nslot = first[n] - k0;
+    std::vector<uint64_t> rfirst(first, first + n + 1);
+    for (uint64_t &f : rfirst)
+        f -= k0;
+    Staging st;
+    const size_t i_d = st.in(bytes(data) + sp.lo, sp.bytes());
+    const size_t i_o = st.in(sp.off.data(), 8 * n);
+    const size_t i_l = st.in(lens, 4 * n);
+    const size_t i_info = st.out(info, sizeof(BRB_MetaDataUnpackInfo) * n);
+    const size_t i_io = st.inout(ioff + k0, 8 * nslot);
+    const size_t i_il = st.inout(ilen + k0, 4 * nslot);
+    const size_t i_id = st.inout(iid + k0, 8 * nslot);
+    const size_t i_sub = st.inout(isub + k0, 8 * nslot);
+    const size_t i_f = st.in(rfirst.data(), 8 * (n + 1));
+    const size_t i_add = st.out(added, 4 * n);
+    return st.run(s, &pf, [&] {
+        return launched(brb::launch_metadata_unpack_items(
+            st.dev(i_d), sp.lo, st.dev<uint64_t>(i_o), st.dev<uint32_t>(i_l), n, st.dev<BRB_MetaDataUnpackInfo>(i_info),
+            st.dev<uint64_t>(i_io), st.dev<uint32_t>(i_il), st.dev<uint64_t>(i_id), st.dev<uint64_t>(i_sub),
+            st.dev<uint64_t>(i_f), st.dev<uint32_t>(i_add), s));
+    });
+}
+
 // MetaDataPack of n packs (metadata_pack_kernels.hip).  Host mode validates the item lists, stages the
 // span of the items and -- in both directions, so the bytes between packs survive -- the span of the
 // packs, as b64_batch stages its outputs.

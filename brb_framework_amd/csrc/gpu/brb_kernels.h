@@ -59,6 +59,12 @@ hipError_t launch_digest_stream_segments(bool sha1, uint8_t *ctxs, const uint32_
 // MetaDataUnpack of whole packs (metadata_kernels.hip): pack r = data[offs[r] .. + lens[r])
 hipError_t launch_metadata_unpack(const uint8_t *data, const uint64_t *offs, const uint32_t *lens, uint64_t n,
                                   BRB_MetaDataUnpackInfo *info, hipStream_t s);
+// ... and the item table (BRB_MetaDataUnpackItemsBatch): pack r's MetaDataItemAdd calls in slots first[r] ..
+// first[r + 1] - 1 of ioff / ilen / iid / isub, their number in added[r]; item offsets are data_base + the
+// offset from `data` (host mode stages a span of the caller's buffer).  The same kernels and test options.
+hipError_t launch_metadata_unpack_items(const uint8_t *data, uint64_t data_base, const uint64_t *offs, const uint32_t *lens,
+                                        uint64_t n, BRB_MetaDataUnpackInfo *info, uint64_t *ioff, uint32_t *ilen,
+                                        uint64_t *iid, uint64_t *isub, const uint64_t *first, uint32_t *added, hipStream_t s);
 
 // MetaDataPack of whole packs (metadata_pack_kernels.hip): pack p = items first[p] .. first[p + 1] - 1, item k =
 // data[ioff[k] .. + ilen[k]) with iid[k], isub[k]; written at out + ooff[p]

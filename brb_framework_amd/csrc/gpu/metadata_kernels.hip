@@ -1,6 +1,7 @@
 // metadata_kernels.hip -- batched MetaDataUnpack (libbrb_core/data/utils/meta_data.c:145-328) over
 // many MetaData packs (the mmap'd file cache and encrypted K/V files keep their
-// objects as packs whose MD5 covers the items' data).
+// objects as packs whose MD5 covers the items' data), and -- BRB_MetaDataUnpackItemsBatch -- the item
+// table the reference's unpack builds on the way (Table / Sink below).
 //
 // One lane per pack.  A pack is one sequential byte stream -- header, then per item three 8-byte
 // fields, the data, the 0x1F canary -- whose every position depends on the sizes before it, so the
@@ -62,13 +63,82 @@ struct Ahead {
     BRB_DEV uint64_t qw(int i) const { return uint64_t(dw(i)) | (uint64_t(dw(i + 1)) << 32); }
 };
 
+// The item table of BRB_MetaDataUnpackItemsBatch: the reference's MetaDataItemAdd calls
+// (meta_data.c:246-248), pack r's j-th call in slot first[r] + j while j < first[r + 1] - first[r].
+// `base` is the offset in the caller's data of the byte the kernel's `data` points at (host mode
+// stages a span), so item offsets are the caller's.
+struct Table {
+    uint64_t *off;
+    uint32_t *len;
+    uint64_t *id, *sub;
+    const uint64_t *first;
+    uint32_t *added;
+    uint64_t base;
+};
+
+// Where the walk reports an added item.  Sink<> (BRB_MetaDataUnpackBatch) records nothing and takes
+// no kernel argument: its kernels are the ones without a table.  Sink<Table> stores the four fields
+// from the walking lane -- 28 bytes per item in four plain vector stores, behind the slot bound.
+template <class... Tab>
+struct Sink {
+    static constexpr bool kOn = false;
+    struct Row {};
+    BRB_DEV uint64_t base() const { return 0; }
+    BRB_DEV Row row(bool, uint64_t) const { return Row(); }
+    BRB_DEV void add(const Row &, uint32_t, uint64_t, uint64_t, uint64_t, uint64_t) const {}
+    BRB_DEV void done(uint64_t, uint32_t) const {}
+};
+
+template <>
+struct Sink<Table> {
+    static constexpr bool kOn = true;
+    Table t;
+    struct Row {
+        uint64_t slot0;
+        uint32_t cap;                                 // an item index is below 2^31: a larger count clamps
+    };
+    BRB_DEV explicit Sink(const Table &t_) : t(t_) {}
+    BRB_DEV uint64_t base() const { return t.base; }
+    BRB_DEV Row row(bool valid, uint64_t r) const
+    {
+        Row w = {0, 0};
+        if (valid) {
+            w.slot0 = t.first[r];
+            const uint64_t c = t.first[r + 1] - w.slot0;
+            w.cap = c < 0x80000000ull ? uint32_t(c) : 0x80000000u;
+        }
+        return w;
+    }
+    // item j of the pack: its first data byte at `at` (an offset in the caller's data), sz, the ids
+    BRB_DEV void add(const Row &w, uint32_t j, uint64_t at, uint64_t sz, uint64_t id, uint64_t sub) const
+    {
+        if (j < w.cap) {
+            const uint64_t s = w.slot0 + j;
+            t.off[s] = at;
+            t.len[s] = uint32_t(sz);                  // an accepted sz is <= the pack's uint32 length
+            t.id[s] = id;
+            t.sub[s] = sub;
+        }
+    }
+    BRB_DEV void done(uint64_t r, uint32_t n) const { t.added[r] = n; }
+};
+
+// MetaDataItemAdd calls of a finished walk: every item whose canary held, and the one whose did not
+BRB_DEV uint32_t items_added(int32_t code, uint32_t items)
+{
+    return items + (code == BRB_METADATA_UNPACK_FAILED_CORRUPTED_CANARY ? 1u : 0u);
+}
+
 // MetaDataUnpack of one pack by one lane with per-lane loads (the round-3 kernel's walk): groups
 // whose packs span 2 GiB or more take it inside the line-staged kernel, and the round-3 kernel
-// (test option seg_line = 0) is this function per lane.
-template <uint32_t RW, class Beat = brb_line::NoBeat>
+// (test option seg_line = 0) is this function per lane.  `at`: the pack's offset in the caller's
+// data (the table's item offsets).
+template <uint32_t RW, class Beat = brb_line::NoBeat, class SinkT = Sink<>>
 BRB_DEV BRB_MetaDataUnpackInfo unpack_lane(brb_md5::FunnelT<RW> &f, const uint8_t *base, uint64_t size,
-                                           Beat beat = Beat())
+                                           Beat beat = Beat(), const SinkT &sink = SinkT(), uint64_t r = 0,
+                                           uint64_t at = 0)
 {
+    const typename SinkT::Row row = sink.row(true, r);
     int32_t code;
     uint32_t items = 0;
     uint64_t offset = 0, remaining = 0, needed = 0;   // cur_offset starts at the MemBuffer offset, 0
@@ -85,6 +155,7 @@ BRB_DEV BRB_MetaDataUnpackInfo unpack_lane(brb_md5::FunnelT<RW> &f, const uint8_
         offset = BRB_METADATA_HEADER_SIZE;                  // :198-199
         code = BRB_METADATA_UNPACK_SUCCESS;
         uint64_t sz = hd.qw(20);                            // item 0's sz (bytes 80..87)
+        uint64_t id = hd.qw(16), sub = hd.qw(18);           // its item_id, item_sub_id (the table's only)
         for (int32_t i = 0; i < item_count; i++) {          // :202
             beat();                                         // per item: an empty one runs no block
             remaining = size - offset;                      // :213 (unsigned long)
@@ -100,6 +171,7 @@ BRB_DEV BRB_MetaDataUnpackInfo unpack_lane(brb_md5::FunnelT<RW> &f, const uint8_
                 code = BRB_METADATA_UNPACK_FAILED_NEED_MORE_DATA_OBJECT;
                 break;
             }
+            sink.add(row, items, at + offset, sz, id, sub);  // :246-248 MetaDataItemAdd
             // the canary and the next item's fields (bytes offset + sz .. + 24) load while the data
             // is hashed; the data comes in 64-byte blocks with the next one in flight
             Ahead<7> nx;
@@ -144,6 +216,12 @@ BRB_DEV BRB_MetaDataUnpackInfo unpack_lane(brb_md5::FunnelT<RW> &f, const uint8_
             // next item's sz: pack bytes offset + 16 .. + 23 = bytes 17 .. 24 of nx
             sz = uint64_t(__builtin_amdgcn_alignbit(nx.dw(5), nx.dw(4), 8)) |
                  (uint64_t(__builtin_amdgcn_alignbit(nx.dw(6), nx.dw(5), 8)) << 32);
+            if (SinkT::kOn) {                               // its ids: bytes 1 .. 8 and 9 .. 16 of nx
+                id = uint64_t(__builtin_amdgcn_alignbit(nx.dw(1), nx.dw(0), 8)) |
+                     (uint64_t(__builtin_amdgcn_alignbit(nx.dw(2), nx.dw(1), 8)) << 32);
+                sub = uint64_t(__builtin_amdgcn_alignbit(nx.dw(3), nx.dw(2), 8)) |
+                      (uint64_t(__builtin_amdgcn_alignbit(nx.dw(4), nx.dw(3), 8)) << 32);
+            }
         }
         if (code == BRB_METADATA_UNPACK_SUCCESS) {          // :287-298
             const Md5State st = f.finish();
@@ -151,6 +229,7 @@ BRB_DEV BRB_MetaDataUnpackInfo unpack_lane(brb_md5::FunnelT<RW> &f, const uint8_
                 code = BRB_METADATA_UNPACK_FAILED_DIGEST_INVALID;
         }
     }
+    sink.done(r, items_added(code, items));
     BRB_MetaDataUnpackInfo o;
     o.error_code = code;
     o.item_count = items;
@@ -175,6 +254,24 @@ __global__ __launch_bounds__(kBlock) void metadata_unpack_kernel(const uint8_t *
     info[r] = unpack_lane(f, data + offs[r], lens[r]);
 }
 
+// ... and with the item table (a kernel of its own name, so the one above is the code it was)
+__global__ __launch_bounds__(kBlock) void metadata_unpack_items_kernel(const uint8_t *__restrict__ data,
+                                                                       const uint64_t *__restrict__ offs,
+                                                                       const uint32_t *__restrict__ lens, uint64_t n,
+                                                                       BRB_MetaDataUnpackInfo *__restrict__ info, Table tab)
+{
+    __shared__ __attribute__((aligned(8192))) uint32_t blk[kBlock / 64][brb_md5::kRingWords][64];
+    const Sink<Table> sink(tab);
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint64_t r = uint64_t(blockIdx.x) * kBlock + threadIdx.x;
+    if (r >= n)
+        return;
+    brb_md5::Funnel f;
+    f.init(&blk[wave][0][lane]);
+    const uint64_t at = offs[r];
+    info[r] = unpack_lane(f, data + at, lens[r], brb_line::NoBeat(), sink, r, sink.base() + at);
+}
+
 // Line-staged MetaDataUnpack (round 4; line_stream.h).  A wave unpacks groups of 64 packs, one per
 // lane; a pack's 128-byte lines stream through the LDS-DMA ring, and the lane walks its pack out of
 // the window (lines k-1, k) as a state machine over the reference's loop (meta_data.c:202-282):
@@ -192,14 +289,18 @@ __global__ __launch_bounds__(kBlock) void metadata_unpack_kernel(const uint8_t *
 // (wave W + p) compresses them, pads, checks the digest and writes the info (two ring slots, so that
 // four pairs fit a CU's LDS).
 // STALL: test option pair_stall (pair_fault.h), PC only.
-template <int W, int NS, bool PC, bool STALL = false>
+// Tab = Table: the walking wave (PC: the producer) also writes the item table, an item at its FIELDS
+// -> DATA transition -- where the reference calls MetaDataItemAdd, its ids still in the window -- and
+// items_added at the group's end; the consumer's side of the pair is the same either way.
+template <int W, int NS, bool PC, bool STALL = false, class... Tab>
 __global__ __launch_bounds__(64 * W * (PC ? 2 : 1)) void metadata_line_kernel(const uint8_t *__restrict__ data,
                                                                                const uint64_t *__restrict__ offs,
                                                                                const uint32_t *__restrict__ lens, uint64_t n,
                                                                                BRB_MetaDataUnpackInfo *__restrict__ info,
-                                                                               uint32_t *fault)
+                                                                               uint32_t *fault, Tab... tab)
 {
     using namespace brb_line;
+    const Sink<Tab...> sink{tab...};
     constexpr uint32_t RW = PC ? 64 : brb_line::kRingWords;
     constexpr int WP = PC ? W : 1;                      // pairs' mailbox arrays (1: unused)
     enum : uint32_t { kFields = 0, kData = 1, kCanary = 2, kDone = 3 };
@@ -292,6 +393,8 @@ __global__ __launch_bounds__(64 * W * (PC ? 2 : 1)) void metadata_line_kernel(co
         const bool valid = r < n;
         const uint64_t base = valid ? dbase + offs[r] : dbase;
         const uint64_t size = valid ? lens[r] : 0;
+        const typename Sink<Tab...>::Row row = sink.row(valid, r);
+        const uint64_t at = base - (dbase - sink.base());   // the pack's offset in the caller's data
         const uint32_t a0 = uint32_t(base & 127);
         const uint32_t nl = size ? uint32_t((a0 + size + 127) >> 7) : 0u;
         const uint64_t line0 = base & ~uint64_t(127);
@@ -309,9 +412,10 @@ __global__ __launch_bounds__(64 * W * (PC ? 2 : 1)) void metadata_line_kernel(co
             }
             if (valid) {
                 if (PC)
-                    info[r] = unpack_lane(f, reinterpret_cast<const uint8_t *>(base), size, brb_line::HbBeat{&ev[pr][3], 0});
+                    info[r] = unpack_lane(f, reinterpret_cast<const uint8_t *>(base), size, brb_line::HbBeat{&ev[pr][3], 0},
+                                          sink, r, at);
                 else
-                    info[r] = unpack_lane(f, reinterpret_cast<const uint8_t *>(base), size);
+                    info[r] = unpack_lane(f, reinterpret_cast<const uint8_t *>(base), size, brb_line::NoBeat(), sink, r, at);
             }
             continue;
         }
@@ -372,6 +476,27 @@ __global__ __launch_bounds__(64 * W * (PC ? 2 : 1)) void metadata_line_kernel(co
                                 code = BRB_METADATA_UNPACK_FAILED_NEED_MORE_DATA_OBJECT;
                                 phase = kDone;
                             } else {
+                                if (Sink<Tab...>::kOn) {         // :246-248 MetaDataItemAdd
+                                    // The ids are the 16 bytes before sz, at q.  An item accepted at q < size
+                                    // had 32 bytes left, so they lie inside the pack: five window dwords, one
+                                    // shift, no masks.  Else (a pack shorter than its header, walked past its
+                                    // end) every byte reads as 0.
+                                    const uint64_t q = offset - kItemRaw;
+                                    uint64_t id = 0, sub = 0;
+                                    if (!drain && q < size) {
+                                        const uint32_t wb = uint32_t(int64_t(q) - L0);
+                                        uint32_t d[5];
+#pragma unroll
+                                        for (uint32_t i = 0; i < 5; i++)
+                                            d[i] = win_dword(win, (wb >> 2) + i, sa, sb);
+                                        const uint32_t sh = 8 * (wb & 3);
+                                        id = uint64_t(__builtin_amdgcn_alignbit(d[1], d[0], sh)) |
+                                             (uint64_t(__builtin_amdgcn_alignbit(d[2], d[1], sh)) << 32);
+                                        sub = uint64_t(__builtin_amdgcn_alignbit(d[3], d[2], sh)) |
+                                              (uint64_t(__builtin_amdgcn_alignbit(d[4], d[3], sh)) << 32);
+                                    }
+                                    sink.add(row, uint32_t(item), at + offset, sz, id, sub);
+                                }
                                 ds = offset;
                                 de = offset + sz;
                                 f.total += sz;
@@ -473,6 +598,8 @@ __global__ __launch_bounds__(64 * W * (PC ? 2 : 1)) void metadata_line_kernel(co
             uint32_t dw[36] = {};
             events(int64_t(1) << 62, int64_t(1) << 62, 0, 0, dw, true);
         }
+        if (valid)                                               // by the walking wave: the digest adds no item
+            sink.done(r, items_added(code, items));
         if (PC) {
             const uint32_t v[15] = {uint32_t(f.acc) | (f.nacc << 24), uint32_t(f.total), uint32_t(f.total >> 32),
                                     uint32_t(code), dig[0], dig[1], dig[2], dig[3], items,
@@ -501,17 +628,20 @@ __global__ __launch_bounds__(64 * W * (PC ? 2 : 1)) void metadata_line_kernel(co
     }
 }
 
-}  // namespace
-
-namespace brb {
-
-hipError_t launch_metadata_unpack(const uint8_t *data, const uint64_t *offs, const uint32_t *lens, uint64_t n,
-                                  BRB_MetaDataUnpackInfo *info, hipStream_t s)
+// Tab: none (BRB_MetaDataUnpackBatch) or one Table (BRB_MetaDataUnpackItemsBatch); the same choice of
+// kernel by the test options either way.
+template <class... Tab>
+hipError_t launch_unpack(const uint8_t *data, const uint64_t *offs, const uint32_t *lens, uint64_t n,
+                         BRB_MetaDataUnpackInfo *info, hipStream_t s, Tab... tab)
 {
     if (n == 0)
         return hipSuccess;
     if (brb_opt::get(brb_opt::kSegLine) == 0) {
-        metadata_unpack_kernel<<<unsigned((n + kBlock - 1) / kBlock), kBlock, 0, s>>>(data, offs, lens, n, info);
+        const unsigned grid = unsigned((n + kBlock - 1) / kBlock);
+        if constexpr (sizeof...(Tab) == 0)
+            metadata_unpack_kernel<<<grid, kBlock, 0, s>>>(data, offs, lens, n, info);
+        else
+            metadata_unpack_items_kernel<<<grid, kBlock, 0, s>>>(data, offs, lens, n, info, tab...);
         return hipGetLastError();
     }
     constexpr int W = 4;                               // 4 walking waves: one workgroup per CU
@@ -520,17 +650,36 @@ hipError_t launch_metadata_unpack(const uint8_t *data, const uint64_t *offs, con
     const unsigned grid = unsigned(wgs < brb_digest::device_cu_count() ? wgs : brb_digest::device_cu_count());
     if (brb_opt::get(brb_opt::kSegLine) == 2) {        // wave pairs
         if (brb_opt::get(brb_opt::kPairStall) != 0)
-            metadata_line_kernel<W, 2, true, true><<<grid, 128 * W, 0, s>>>(data, offs, lens, n, info, brb::pair_fault_word());
+            metadata_line_kernel<W, 2, true, true, Tab...>
+                <<<grid, 128 * W, 0, s>>>(data, offs, lens, n, info, brb::pair_fault_word(), tab...);
         else
-            metadata_line_kernel<W, 2, true><<<grid, 128 * W, 0, s>>>(data, offs, lens, n, info, brb::pair_fault_word());
+            metadata_line_kernel<W, 2, true, false, Tab...>
+                <<<grid, 128 * W, 0, s>>>(data, offs, lens, n, info, brb::pair_fault_word(), tab...);
     } else if (brb_opt::get(brb_opt::kLineSlots) == 2) {
         // three slots by default: 43.6 vs 49.3 us with two (bench --op metadata, interleaved A/B,
         // profiles/r04/ab/r04s_md); test option line_slots 2 for the other
-        metadata_line_kernel<W, 2, false><<<grid, 64 * W, 0, s>>>(data, offs, lens, n, info, nullptr);
+        metadata_line_kernel<W, 2, false, false, Tab...><<<grid, 64 * W, 0, s>>>(data, offs, lens, n, info, nullptr, tab...);
     } else {
-        metadata_line_kernel<W, 3, false><<<grid, 64 * W, 0, s>>>(data, offs, lens, n, info, nullptr);
+        metadata_line_kernel<W, 3, false, false, Tab...><<<grid, 64 * W, 0, s>>>(data, offs, lens, n, info, nullptr, tab...);
     }
     return hipGetLastError();
+}
+
+}  // namespace
+
+namespace brb {
+
+hipError_t launch_metadata_unpack(const uint8_t *data, const uint64_t *offs, const uint32_t *lens, uint64_t n,
+                                  BRB_MetaDataUnpackInfo *info, hipStream_t s)
+{
+    return launch_unpack(data, offs, lens, n, info, s);
+}
+
+hipError_t launch_metadata_unpack_items(const uint8_t *data, uint64_t data_base, const uint64_t *offs, const uint32_t *lens,
+                                        uint64_t n, BRB_MetaDataUnpackInfo *info, uint64_t *ioff, uint32_t *ilen,
+                                        uint64_t *iid, uint64_t *isub, const uint64_t *first, uint32_t *added, hipStream_t s)
+{
+    return launch_unpack(data, offs, lens, n, info, s, Table{ioff, ilen, iid, isub, first, added, data_base});
 }
 
 }  // namespace brb

@@ -15,8 +15,11 @@ from the item lists.  pack_batch is the earlier host-side builder: it lays packs
 the host and computes every header digest with one BRB_MD5BatchSegments call whose segments are the
 item data inside the packed buffer itself.
 unpack_batch is BRB_MetaDataUnpackBatch (one GPU lane per pack; reference return codes and
-MetaDataUnpackerInfo fields, quirks included -- include/brb_crypto.h).  items() lists a pack's items
-on the host, for packs unpack_batch accepted."""
+MetaDataUnpackerInfo fields, quirks included -- include/brb_crypto.h).  unpack_items_batch is
+BRB_MetaDataUnpackItemsBatch: the same check, and the item table the reference's unpack builds (offset,
+length, id and sub-id of every MetaDataItemAdd call) written by the walking lane, in the arrays the pack
+and segment-digest calls take.  items() lists one pack's items on the host, for packs unpack_batch
+accepted."""
 import struct
 
 import numpy as np
@@ -110,6 +113,46 @@ def unpack_batch(buf, offsets, lengths, stream=None, all_devices=False):
     cur_remaining, cur_needed) per pack, error_code a MetaDataUnpackReturnCode (7 = SUCCESS)."""
     return crypto.metadata_unpack_batch(buf, np.asarray(offsets, np.uint64), np.asarray(lengths, np.uint32),
                                         stream=stream, all_devices=all_devices)
+
+
+def max_items_bound(lengths):
+    """Slots that always hold a pack's item table: an added item takes at least 25 bytes after the header,
+    (len - 64) // 25; a pack shorter than its header adds at most one (the zeros past its end)."""
+    n = np.asarray(lengths, np.int64)
+    return np.where(n >= HEADER, (n - HEADER) // (ITEM_RAW + 1), 1).astype(np.uint64)
+
+
+def unpack_items_batch(buf, offsets, lengths, max_items=None, stream=None, all_devices=False):
+    """BRB_MetaDataUnpackItemsBatch: unpack_batch plus the item table MetaDataUnpack builds (one entry per
+    MetaDataItemAdd call, reference order).  Every pack gets max_items table slots, or with max_items None
+    the max_items_bound of its length, which always suffices.  Returns (info, items_added, pack_first_slot,
+    item_offsets, item_lengths, item_ids, item_sub_ids): pack p's items are slots pack_first_slot[p] ..
+    + min(items_added[p], its slot count) - 1 of the four arrays (item_offsets: offsets in `buf` of each
+    item's data); items_added[p] above the slot count means the table of pack p is cut short; slots past
+    items_added[p] hold 0.  With a CUDA tensor `buf` (offsets int64, lengths int32 tensors) everything
+    returned is a tensor on its device; the slot layout is made on the host (max_items None: from the
+    lengths, read back once) and uploaded, the packs and the table stay in HBM."""
+    n = len(offsets)
+    dev = crypto._is_torch(buf)
+    if max_items is None:
+        per = max_items_bound(lengths.cpu().numpy() if dev else lengths)
+    else:
+        per = np.full(n, int(max_items), np.uint64)
+    first = np.zeros(n + 1, np.uint64)
+    np.cumsum(per, out=first[1:])
+    slots = int(first[n])
+    if dev:
+        import torch
+        z = lambda dt: torch.zeros(slots, dtype=dt, device=buf.device)
+        table = [z(torch.int64), z(torch.int32), z(torch.int64), z(torch.int64)]
+        first = torch.from_numpy(first.view(np.int64)).to(buf.device)
+    else:
+        offsets, lengths = np.asarray(offsets, np.uint64), np.asarray(lengths, np.uint32)
+        table = [np.zeros(slots, np.uint64), np.zeros(slots, np.uint32), np.zeros(slots, np.uint64),
+                 np.zeros(slots, np.uint64)]
+    info, added = crypto.metadata_unpack_items_batch(buf, offsets, lengths, *table, first, stream=stream,
+                                                     all_devices=all_devices)
+    return (info, added, first, *table)
 
 
 def items(pack: bytes):

@@ -203,6 +203,37 @@ typedef struct BRB_MetaDataUnpackInfo {
 int BRB_MetaDataUnpackBatch(const void *data, const uint64_t *offsets, const uint32_t *lengths, uint64_t n_packs,
                             BRB_MetaDataUnpackInfo *info, unsigned flags, void *hip_stream);
 
+/* BRB_MetaDataUnpackBatch plus the item table MetaDataUnpack builds while it checks: one entry per
+ * MetaDataItemAdd call (meta_data.c:246-248), in the reference's order -- every item that passed both
+ * bounds checks (32 bytes left for its header; sz + 1 bytes left for its data, and sz <= the pack's
+ * length), whatever happens next: an item whose canary then proves corrupted is in the table, and so
+ * are all items of a pack whose digest then fails; the item at which a NEED_MORE_DATA_* code was
+ * decided is not.  info[p] is what BRB_MetaDataUnpackBatch writes for the pack, field for field.
+ * items_added[p] is the number of such calls, = info[p].item_count + (error_code == CORRUPTED_CANARY),
+ * 0 for a bad magic.  Pack p owns table slots pack_first_slot[p] .. pack_first_slot[p+1]-1 (n_packs + 1
+ * entries, non-decreasing) of the four arrays; its j-th item, for j below its slot count, is written
+ * to slot s = pack_first_slot[p] + j:
+ *   item_offsets[s]  the offset in `data` of the item's first data byte (the reference's ptr; valid
+ *                    for sz == 0 too), item_lengths[s] = sz,
+ *   item_ids[s], item_sub_ids[s]  its two unsigned long fields (bytes past the pack read as 0).
+ * Items past the slot count are counted, not stored: items_added[p] > the slot count says so, and
+ * (lengths[p] - 64) / 25 slots are always enough for a pack of at least 64 bytes (a shorter one adds
+ * at most one item: the zero bytes past its end, read as an empty item whose canary is missing).
+ * Slots j >= items_added[p] keep their values, in both modes, and no slot of another pack is
+ * touched.  The arrays have the element
+ * types of BRB_MetaDataPackBatch and BRB_MD5BatchSegments: item_offsets / item_lengths / item_ids /
+ * item_sub_ids with pack_first_slot as pack_first_item (exact slot counts) repack, and item_offsets /
+ * item_lengths are segment lists, with nothing leaving HBM in device mode.
+ * Flags, return codes, hip_stream and the device-mode contract are BRB_MetaDataUnpackBatch's (device
+ * mode checks NULL pointers, the count and the flags, and allocates nothing).  Host mode: -1 for a
+ * pack_first_slot that decreases; the four arrays are staged over slots [pack_first_slot[0],
+ * pack_first_slot[n_packs]) in both directions.  BRB_BATCH_ALL_DEVICES always splits (contiguous pack
+ * ranges own contiguous slot ranges).  After BRB_BATCH_FAULT the table is unspecified. */
+int BRB_MetaDataUnpackItemsBatch(const void *data, const uint64_t *offsets, const uint32_t *lengths, uint64_t n_packs,
+                                 BRB_MetaDataUnpackInfo *info, uint64_t *item_offsets, uint32_t *item_lengths,
+                                 uint64_t *item_ids, uint64_t *item_sub_ids, const uint64_t *pack_first_slot,
+                                 uint32_t *items_added, unsigned flags, void *hip_stream);
+
 /* MetaDataPack (meta_data.c:104-140, digest :397-433) for n_packs MetaDatas.  Pack p holds items
  * pack_first_item[p] .. pack_first_item[p+1]-1 (n_packs + 1 entries, non-decreasing); item k =
  * data[item_offsets[k] .. + item_lengths[k]) with item_ids[k], item_sub_ids[k].  Pack p is written
