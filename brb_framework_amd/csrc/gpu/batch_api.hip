@@ -239,6 +239,89 @@ bool parts_disjoint(const uint64_t *offs, const LenT *lens, uint64_t n, uint64_t
     return true;
 }
 
+// A host-mode "first" list (item i owns [first[i], first[i + 1])), checked: the range [k0, k0 + count) of
+// the caller's arrays it covers and, made where the call stages, the copy rebased to start at 0.  !ok: not
+// non-decreasing (the error names the list), or each(i), run after item i's check, refused (its own error).
+struct FirstList {
+    const uint64_t *first;
+    uint64_t n, k0, count;
+    bool ok;
+    std::vector<uint64_t> rebased() const
+    {
+        std::vector<uint64_t> rel(first, first + n + 1);
+        for (uint64_t &f : rel)
+            f -= k0;
+        return rel;
+    }
+};
+
+template <class Each>
+FirstList first_list(const uint64_t *first, uint64_t n, const char *name, Each each)
+{
+    FirstList fl{first, n, first[0], first[n] - first[0], false};
+    for (uint64_t i = 0; i < n; i++) {
+        if (first[i + 1] < first[i]) {
+            set_err("%s is not non-decreasing at %llu", name, (unsigned long long)i);
+            return fl;
+        }
+        if (!each(i))
+            return fl;
+    }
+    fl.ok = true;
+    return fl;
+}
+
+FirstList first_list(const uint64_t *first, uint64_t n, const char *name)
+{
+    return first_list(first, n, name, [](uint64_t) { return true; });
+}
+
+// The contexts a host-mode call names in a context table: item i acts on ctxs[ix ? ix[i] : i].  ok() checks
+// the index list (dup_hint: what to do instead of naming a context twice); gather() is what the call stages
+// in both directions, the named contexts in item order, so the kernel runs without an index; scatter() puts
+// them back after a run that succeeded.
+struct NamedCtx {
+    uint8_t *ctxs;
+    const uint32_t *ix;
+    uint64_t n;
+    size_t stride;
+    std::vector<uint8_t> rows;
+
+    bool ok(uint64_t n_ctx, const char *dup_hint) const
+    {
+        if (!ix) {
+            if (n > n_ctx)
+                set_err("ctx_index is NULL and n (%llu) > n_ctx (%llu)", (unsigned long long)n, (unsigned long long)n_ctx);
+            return n <= n_ctx;
+        }
+        for (uint64_t i = 0; i < n; i++)
+            if (ix[i] >= n_ctx) {
+                set_err("item %llu: ctx_index %u out of range (%llu contexts)", (unsigned long long)i, ix[i],
+                        (unsigned long long)n_ctx);
+                return false;
+            }
+        std::vector<uint32_t> sorted(ix, ix + n);
+        std::sort(sorted.begin(), sorted.end());
+        const auto dup = std::adjacent_find(sorted.begin(), sorted.end());
+        if (dup != sorted.end())
+            set_err("context %u is named twice (%s)", *dup, dup_hint);
+        return dup == sorted.end();
+    }
+    uint8_t *gather()
+    {
+        rows.resize(ix ? n * stride : 0);
+        for (uint64_t i = 0; ix && i < n; i++)
+            memcpy(rows.data() + i * stride, ctxs + ix[i] * stride, stride);
+        return ix ? rows.data() : ctxs;
+    }
+    int scatter(int rc) const
+    {
+        for (uint64_t i = 0; rc == BRB_BATCH_OK && ix && i < n; i++)
+            memcpy(ctxs + ix[i] * stride, rows.data() + i * stride, stride);
+        return rc;
+    }
+};
+
 // ---- digests ------------------------------------------------------------------------------------
 using VarLauncher = hipError_t (*)(const uint8_t *, const uint64_t *, const uint32_t *, uint64_t, uint8_t *,
                                    hipStream_t);
@@ -331,25 +414,9 @@ int digest_stream(bool sha1, StreamOp op, void *ctxs, uint64_t n_ctx, const uint
         return device_run(launch(bytes(ctxs), ctx_index, bytes(data), offsets, lengths, bytes(digests)), s, flags);
     }
     // host mode: every list is host memory and is checked before anything runs
-    if (!ctx_index && n > n_ctx) {
-        set_err("ctx_index is NULL and n (%llu) > n_ctx (%llu)", (unsigned long long)n, (unsigned long long)n_ctx);
+    NamedCtx named{bytes(ctxs), ctx_index, n, stride, {}};
+    if (!named.ok(n_ctx, "two pieces of one chain in one call is a race"))
         return BRB_BATCH_BADARG;
-    }
-    if (ctx_index) {
-        for (uint64_t i = 0; i < n; i++)
-            if (ctx_index[i] >= n_ctx) {
-                set_err("item %llu: ctx_index %u out of range (%llu contexts)", (unsigned long long)i, ctx_index[i],
-                        (unsigned long long)n_ctx);
-                return BRB_BATCH_BADARG;
-            }
-        std::vector<uint32_t> sorted(ctx_index, ctx_index + n);
-        std::sort(sorted.begin(), sorted.end());
-        const auto dup = std::adjacent_find(sorted.begin(), sorted.end());
-        if (dup != sorted.end()) {
-            set_err("context %u is named twice (two pieces of one chain in one call is a race)", *dup);
-            return BRB_BATCH_BADARG;
-        }
-    }
     Span sp;
     if (op == kStreamUpdate) {
         sp = span_rebase(offsets, lengths, n);
@@ -369,26 +436,16 @@ int digest_stream(bool sha1, StreamOp op, void *ctxs, uint64_t n_ctx, const uint
                                  lengths ? lengths + lo : nullptr, hi - lo, digests ? bytes(digests) + lo * dig : nullptr,
                                  flags & ~BRB_BATCH_ALL_DEVICES, nullptr);
         });
-    std::vector<uint8_t> named;                      // the named contexts in item order
-    if (ctx_index) {
-        named.resize(n * stride);
-        for (uint64_t i = 0; i < n; i++)
-            memcpy(named.data() + i * stride, bytes(ctxs) + ctx_index[i] * stride, stride);
-    }
     Staging st;
-    const size_t i_c = st.inout(ctx_index ? named.data() : bytes(ctxs), n * stride);
+    const size_t i_c = st.inout(named.gather(), n * stride);
     const size_t i_d = op == kStreamUpdate ? st.in(data ? bytes(data) + sp.lo : nullptr, sp.bytes()) : 0;
     const size_t i_o = op == kStreamUpdate ? st.in(sp.off.data(), 8 * n) : 0;
     const size_t i_l = op == kStreamUpdate ? st.in(lengths, 4 * n) : 0;
     const size_t i_g = op == kStreamFinal && digests ? st.out(digests, dig * n) : 0;
-    const int rc = st.run(s, nullptr, [&] {
+    return named.scatter(st.run(s, nullptr, [&] {
         return launched(launch(st.dev(i_c), nullptr, st.dev(i_d), st.dev<uint64_t>(i_o), st.dev<uint32_t>(i_l),
                                op == kStreamFinal && digests ? st.dev(i_g) : nullptr));
-    });
-    if (rc == BRB_BATCH_OK && ctx_index)
-        for (uint64_t i = 0; i < n; i++)
-            memcpy(bytes(ctxs) + ctx_index[i] * stride, named.data() + i * stride, stride);
-    return rc;
+    }));
 }
 
 // BRB_MD5UpdateSegmentsBatch / BrbSha1_UpdateSegmentsBatch: item i advances ctxs[ctx_index ? ctx_index[i] : i] by
@@ -420,31 +477,13 @@ int digest_stream_segments(bool sha1, void *ctxs, uint64_t n_ctx, const uint32_t
                           s, flags);
     }
     // host mode: every list is host memory and is checked before anything runs
-    if (!ctx_index && n > n_ctx) {
-        set_err("ctx_index is NULL and n (%llu) > n_ctx (%llu)", (unsigned long long)n, (unsigned long long)n_ctx);
+    NamedCtx named{bytes(ctxs), ctx_index, n, stride, {}};
+    if (!named.ok(n_ctx, "a chain's pieces of one call go in its segment list"))
         return BRB_BATCH_BADARG;
-    }
-    if (ctx_index) {
-        for (uint64_t i = 0; i < n; i++)
-            if (ctx_index[i] >= n_ctx) {
-                set_err("item %llu: ctx_index %u out of range (%llu contexts)", (unsigned long long)i, ctx_index[i],
-                        (unsigned long long)n_ctx);
-                return BRB_BATCH_BADARG;
-            }
-        std::vector<uint32_t> sorted(ctx_index, ctx_index + n);
-        std::sort(sorted.begin(), sorted.end());
-        const auto dup = std::adjacent_find(sorted.begin(), sorted.end());
-        if (dup != sorted.end()) {
-            set_err("context %u is named twice (a chain's pieces of one call go in its segment list)", *dup);
-            return BRB_BATCH_BADARG;
-        }
-    }
-    for (uint64_t i = 0; i < n; i++)
-        if (first[i + 1] < first[i]) {
-            set_err("item_first_seg is not non-decreasing at %llu", (unsigned long long)i);
-            return BRB_BATCH_BADARG;
-        }
-    const uint64_t k0 = first[0], nseg = first[n] - k0;
+    const FirstList fl = first_list(first, n, "item_first_seg");
+    if (!fl.ok)
+        return BRB_BATCH_BADARG;
+    const uint64_t k0 = fl.k0, nseg = fl.count;
     const Span sp = span_rebase(soff + k0, slen + k0, nseg);
     if (!sp.ok)
         return BRB_BATCH_BADARG;
@@ -461,32 +500,20 @@ int digest_stream_segments(bool sha1, void *ctxs, uint64_t n_ctx, const uint32_t
                                           fin ? fin + lo : nullptr, digests ? bytes(digests) + lo * dig : nullptr,
                                           flags & ~BRB_BATCH_ALL_DEVICES, nullptr);
         });
-    std::vector<uint8_t> named;                      // the named contexts in item order
-    if (ctx_index) {
-        named.resize(n * stride);
-        for (uint64_t i = 0; i < n; i++)
-            memcpy(named.data() + i * stride, bytes(ctxs) + ctx_index[i] * stride, stride);
-    }
-    std::vector<uint64_t> rfirst(first, first + n + 1);
-    for (uint64_t &f : rfirst)
-        f -= k0;
+    const std::vector<uint64_t> rfirst = fl.rebased();
     Staging st;
-    const size_t i_c = st.inout(ctx_index ? named.data() : bytes(ctxs), n * stride);
+    const size_t i_c = st.inout(named.gather(), n * stride);
     const size_t i_d = st.in(data ? bytes(data) + sp.lo : nullptr, sp.bytes());
     const size_t i_o = st.in(sp.off.data(), 8 * nseg);
     const size_t i_l = st.in(slen + k0, 4 * nseg);
     const size_t i_f = st.in(rfirst.data(), 8 * (n + 1));
     const size_t i_n = fin ? st.in(fin, n) : 0;
     const size_t i_g = digests ? st.inout(digests, dig * n) : 0;
-    const int rc = st.run(s, nullptr, [&] {
+    return named.scatter(st.run(s, nullptr, [&] {
         return launched(brb::launch_digest_stream_segments(sha1, st.dev(i_c), nullptr, st.dev(i_d), st.dev<uint64_t>(i_o),
                                                            st.dev<uint32_t>(i_l), st.dev<uint64_t>(i_f), n,
                                                            fin ? st.dev(i_n) : nullptr, digests ? st.dev(i_g) : nullptr, s));
-    });
-    if (rc == BRB_BATCH_OK && ctx_index)
-        for (uint64_t i = 0; i < n; i++)
-            memcpy(bytes(ctxs) + ctx_index[i] * stride, named.data() + i * stride, stride);
-    return rc;
+    }));
 }
 
 int blowfish_batch(const BRB_BLOWFISH_CTX *ctx, unsigned long *words, uint64_t n_blocks, unsigned flags,
@@ -1059,18 +1086,14 @@ int BRB_MD5BatchSegments(const void *data, const uint64_t *soff, const uint32_t 
     if (flags & BRB_BATCH_DEVICE)
         return device_run(brb::launch_md5_segments(bytes(data), soff, slen, first, n_rec, bytes(digests), s), s, flags, &pf);
     // host mode: rebase the segment lists to start at 0 and copy the byte span they cover
-    const uint64_t k0 = first[0], nseg = first[n_rec] - k0;
-    for (uint64_t i = 0; i < n_rec; i++)
-        if (first[i + 1] < first[i]) {
-            set_err("rec_first_seg is not non-decreasing at %llu", (unsigned long long)i);
-            return BRB_BATCH_BADARG;
-        }
+    const FirstList fl = first_list(first, n_rec, "rec_first_seg");
+    if (!fl.ok)
+        return BRB_BATCH_BADARG;
+    const uint64_t k0 = fl.k0, nseg = fl.count;
     const Span sp = span_rebase(soff + k0, slen + k0, nseg);
     if (!sp.ok)
         return BRB_BATCH_BADARG;
-    std::vector<uint64_t> rfirst(first, first + n_rec + 1);
-    for (uint64_t &f : rfirst)
-        f -= k0;
+    const std::vector<uint64_t> rfirst = fl.rebased();
     Staging st;
     const size_t i_d = st.in(bytes(data) + sp.lo, sp.bytes());
     const size_t i_o = st.in(sp.off.data(), 8 * nseg);
@@ -1149,11 +1172,9 @@ int BRB_MetaDataUnpackItemsBatch(const void *data, const uint64_t *offs, const u
                           s, flags, &pf);
     }
     // host mode: the slot list and the packs' span are host memory, so they are checked before anything runs
-    for (uint64_t p = 0; p < n; p++)
-        if (first[p + 1] < first[p]) {
-            set_err("pack_first_slot is not non-decreasing at %llu", (unsigned long long)p);
-            return BRB_BATCH_BADARG;
-        }
+    const FirstList fl = first_list(first, n, "pack_first_slot");
+    if (!fl.ok)
+        return BRB_BATCH_BADARG;
     const Span sp = span_rebase(offs, lens, n);
     if (!sp.ok)
         return BRB_BATCH_BADARG;
@@ -1165,10 +1186,8 @@ int BRB_MetaDataUnpackItemsBatch(const void *data, const uint64_t *offs, const u
                                                 first + lo, added + lo, flags & ~BRB_BATCH_ALL_DEVICES, nullptr);
         });
     const PairFault pf(flags);
-    const uint64_t k0 = first[0], nslot = first[n] - k0;
-    std::vector<uint64_t> rfirst(first, first + n + 1);
-    for (uint64_t &f : rfirst)
-        f -= k0;
+    const uint64_t k0 = fl.k0, nslot = fl.count;
+    const std::vector<uint64_t> rfirst = fl.rebased();
     Staging st;
     const size_t i_d = st.in(bytes(data) + sp.lo, sp.bytes());
     const size_t i_o = st.in(sp.off.data(), 8 * n);
@@ -1213,15 +1232,11 @@ int BRB_MetaDataPackBatch(const void *data, const uint64_t *ioff, const uint32_t
     }
     // host mode: the item lists are host memory, so they are checked before anything runs
     std::vector<uint32_t> plen(n);              // pack sizes (a pack the unpack call can take: a uint32 length)
-    for (uint64_t p = 0; p < n; p++) {
-        if (first[p + 1] < first[p]) {
-            set_err("pack_first_item is not non-decreasing at %llu", (unsigned long long)p);
-            return BRB_BATCH_BADARG;
-        }
+    const FirstList fl = first_list(first, n, "pack_first_item", [&](uint64_t p) {   // per pack, in the list's order
         if (first[p + 1] - first[p] > uint64_t(INT32_MAX)) {
             set_err("pack %llu: %llu items (the header's item count is an int)", (unsigned long long)p,
                     (unsigned long long)(first[p + 1] - first[p]));
-            return BRB_BATCH_BADARG;
+            return false;
         }
         uint64_t size = BRB_METADATA_HEADER_SIZE;
         for (uint64_t k = first[p]; k < first[p + 1]; k++)
@@ -1229,10 +1244,13 @@ int BRB_MetaDataPackBatch(const void *data, const uint64_t *ioff, const uint32_t
         if (size > UINT32_MAX) {
             set_err("pack %llu: %llu bytes (host mode packs at most 4 GiB - 1, the unpack call's length)",
                     (unsigned long long)p, (unsigned long long)size);
-            return BRB_BATCH_BADARG;
+            return false;
         }
         plen[p] = uint32_t(size);
-    }
+        return true;
+    });
+    if (!fl.ok)
+        return BRB_BATCH_BADARG;
     if (int ok = device_ok(); ok != BRB_BATCH_OK)
         return ok;
     if (flags & BRB_BATCH_ALL_DEVICES) {   // packs are written back: their spans must not interleave
@@ -1242,13 +1260,11 @@ int BRB_MetaDataPackBatch(const void *data, const uint64_t *ioff, const uint32_t
                 return BRB_MetaDataPackBatch(data, ioff, ilen, iid, isub, first + lo, hi - lo, out, ooff + lo, flags, nullptr);
             });
     }
-    const uint64_t k0 = first[0], nitem = first[n] - k0;
+    const uint64_t k0 = fl.k0, nitem = fl.count;
     const Span si = span_rebase(ioff + k0, ilen + k0, nitem), so = span_rebase(ooff, plen.data(), n);
     if (!si.ok || !so.ok)
         return BRB_BATCH_BADARG;
-    std::vector<uint64_t> rfirst(first, first + n + 1);
-    for (uint64_t &f : rfirst)
-        f -= k0;
+    const std::vector<uint64_t> rfirst = fl.rebased();
     Staging st;
     const size_t i_d = st.in(bytes(data) + si.lo, si.bytes());
     const size_t i_out = st.inout(bytes(out) + so.lo, so.bytes());

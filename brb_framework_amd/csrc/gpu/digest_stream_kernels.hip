@@ -15,12 +15,13 @@
 //
 // Segments: item i advances its context by a LIST of segments and is then, optionally,
 // finalised -- Update, Final, the fused last piece and the whole-record segment digest in one kernel.
-// The bytes go through the lane's word funnel (stream_funnel.h), seeded from the context.
+// The bytes go through the lane's word funnel (word_funnel.h), seeded from the context, along the shared
+// segment walk (seg_walk.h).
 #include "brb_kernels.h"
 #include "byte_stream.h"
 #include "md5_device.h"
+#include "seg_walk.h"
 #include "sha1_device.h"
-#include "stream_funnel.h"
 
 namespace {
 
@@ -68,8 +69,7 @@ BRB_DEV uint32_t hex4(uint32_t v)
 
 // A context is kHdr header words -- the state, then the two counters -- followed by the 64-byte block
 // buffer; `h` below is the header as loaded.
-struct Md5Stream {                                  // BRB_MD5_CTX: buf[4], bytes[2], in[16], digest[16], string[64]
-    using State = Md5State;
+struct Md5Stream : Md5Words {                       // BRB_MD5_CTX: buf[4], bytes[2], in[16], digest[16], string[64]
     static constexpr uint32_t kHdr = 6, kCtxBytes = 168;
 
     static BRB_DEV State state(const uint32_t (&h)[kHdr]) { return State{h[0], h[1], h[2], h[3]}; }
@@ -93,7 +93,6 @@ struct Md5Stream {                                  // BRB_MD5_CTX: buf[4], byte
         h[4] = old + len;
         h[5] += h[4] < old ? 1u : 0u;
     }
-    static BRB_DEV void compress(State &st, uint32_t (&w)[16]) { md5_compress(st, w); }
     // final() leaves bytes as they are in memory: a call that advanced them before it stores them
     static BRB_DEV void store_counts(uint8_t *cx, const uint32_t (&h)[kHdr])
     {
@@ -291,11 +290,7 @@ __global__ __launch_bounds__(kBlock) void stream_final_kernel(uint8_t *ctxs, con
 }
 
 // Item i: the segments first[i] .. first[i + 1] - 1 into its context, in order, then Final when fin[i].
-// seg_lane's walk (md5_seg_kernels.hip) on a funnel seeded from the context: segment k is read in
-// 64-byte blocks as a range that starts e_k = (message bytes before it) mod 4 bytes early, so its words
-// fall on message word boundaries; those e bytes are the carried ones, never loaded from below the
-// segment.  The next non-empty segment's first block is in flight while the current one is hashed, and an
-// empty segment is skipped without forming an address.  The counters advance once per segment.
+// The shared walk (seg_walk.h) on a funnel seeded from the context.  The counters advance once per segment.
 template <class A>
 __global__ __launch_bounds__(kBlock) void stream_segments_kernel(uint8_t *ctxs, const uint32_t *__restrict__ ctx_index,
                                                                  const uint8_t *__restrict__ data,
@@ -304,7 +299,7 @@ __global__ __launch_bounds__(kBlock) void stream_segments_kernel(uint8_t *ctxs, 
                                                                  const uint64_t *__restrict__ first, uint64_t n,
                                                                  const uint8_t *__restrict__ fin, uint8_t *digests)
 {
-    __shared__ __attribute__((aligned(8192))) uint32_t ring[kBlock / 64][brb_stream::kRingWords][64];   // 8 KiB per wave
+    __shared__ __attribute__((aligned(8192))) uint32_t ring[kBlock / 64][brb_funnel::kRingWords][64];   // 8 KiB per wave
     const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const uint64_t i = uint64_t(blockIdx.x) * kBlock + threadIdx.x;
     if (i >= n)
@@ -317,70 +312,14 @@ __global__ __launch_bounds__(kBlock) void stream_segments_kernel(uint8_t *ctxs, 
     uint32_t h[A::kHdr], in[16];
     load_words(cx, h);
     load_words(cx + 4 * A::kHdr, in);
-    // the next segment with bytes, its length and offset (an empty one's offset is read, never used)
-    auto find = [&](uint64_t kk, uint32_t &len, uint64_t &off) {
-        while (kk < k1) {
-            len = slen[kk];
-            off = soff[kk];
-            if (len)
-                break;
-            kk++;
-        }
-        return kk;
-    };
-    auto start = [&](brb_io::BlockSrc &src, uint64_t off, uint32_t len, uint32_t pre) {
-        const uint8_t *a = data + off;
-        const uint32_t e = pre & 3;
-        src.init(a - e, uint64_t(len) + e, a);
-    };
-    brb_io::BlockSrc sa, sb;
-    uint32_t la = 0, lb = 0;
-    uint64_t oa = 0, ob = 0;
-    uint64_t k = find(k0, la, oa);
-    if (k >= k1 && !last)                           // no bytes, no final: the context is not written
-        return;
+    brb_line::NoBeat beat;
+    brb_funnel::SegWalk walk{data, soff, slen, k1};
     const uint32_t have = A::have(h);
-    uint32_t before = have;                         // message bytes before the segment, mod 4
-    if (k < k1)
-        start(sa, oa, la, before);
-    brb_stream::Funnel<A> f;
+    if (!walk.first(k0, have, beat) && !last)       // no bytes, no final: the context is not written
+        return;
+    brb_funnel::Funnel<A> f;
     f.seed(&ring[wave][0][lane], A::state(h), in, have);
-
-    auto run = [&](brb_io::BlockSrc &src, uint32_t len) {   // 64-byte blocks, the next one in flight
-        const uint64_t nb = uint64_t(len) + f.nacc;
-        for (uint64_t c = 0; c < nb; c += 64) {
-            uint32_t w[16];
-            src.fetch(w);
-            if (c == 0)
-                w[0] = f.head(w[0]);
-            const uint64_t left = nb - c;
-            bool direct = false;
-            if (left >= 64)
-                direct = f.put_block(w);
-            else
-                f.put_tail(w, uint32_t(left));
-            f.pump(w, direct);
-        }
-        if ((nb & 63) == 0) {                       // ended on a whole block: nothing carried
-            f.acc = 0;
-            f.nacc = 0;
-        }
-        A::advance(h, len);
-    };
-    while (k < k1) {
-        const uint64_t kb = find(k + 1, lb, ob);
-        if (kb < k1)
-            start(sb, ob, lb, before + la);
-        run(sa, la);
-        before += la;
-        if (kb >= k1)
-            break;
-        k = find(kb + 1, la, oa);               // sb's length is lb: la is free
-        if (k < k1)
-            start(sa, oa, la, before + lb);
-        run(sb, lb);
-        before += lb;
-    }
+    walk.template run<true>(f, beat, [&](uint32_t len) { A::advance(h, len); });
 
     f.pump();                                       // fewer than 16 words pending
     uint32_t w[16];

@@ -15,7 +15,7 @@
 //
 // Consumption: iteration k reads the 33-dword window of lines k-1 and k (slots (k-1) & 1, k & 1)
 // and EMITS the message words of the lane's current range that start in line k-1, into the lane's
-// 64-word funnel ring (md5_funnel.h FunnelT<64>); whole 16-word blocks are then compressed from the
+// funnel ring (word_funnel.h Md5Funnel<RW>); whole 16-word blocks are then compressed from the
 // ring.  A range is read on a word grid that starts e = (message bytes before it) mod 4 bytes
 // before the range (as the per-lane kernels do), so message words are one v_alignbit of two window
 // dwords each and the first word's low e bytes are the carried ones (Funnel::head).  A word is
@@ -25,10 +25,12 @@
 #pragma once
 
 #include "digest_line.h"
-#include "md5_funnel.h"
+#include "word_funnel.h"
 #include "pair_sync.h"
 
 namespace brb_line {
+
+using brb_funnel::Md5Funnel;
 
 constexpr uint32_t kSlot = 8192;          // one ring slot: 64 rows x one 128-byte line
 constexpr uint32_t kSlots = 3;            // line j in slot j % 3: line k+1 lands during line k-1's work
@@ -182,7 +184,7 @@ struct Emit {
 };
 
 template <uint32_t RW>
-BRB_DEV void plan_range(const brb_md5::FunnelT<RW> &f, bool first, uint32_t ss, uint32_t endr, uint32_t &b, Emit &p)
+BRB_DEV void plan_range(const Md5Funnel<RW> &f, bool first, uint32_t ss, uint32_t endr, uint32_t &b, Emit &p)
 {
     int o;                                                    // grid offset of the first word (-3..127)
     uint32_t e = 0;
@@ -232,7 +234,7 @@ BRB_DEV void edge_words(const Win &w, uint32_t sa, uint32_t sb, Emit &p)
 // A line wholly inside the lane's current range, not its first line and not the line of its last
 // word (the common case): 32 whole words, no head, no tail.
 template <uint32_t RW>
-BRB_DEV void plan_whole(const brb_md5::FunnelT<RW> &f, uint32_t b, Emit &p)
+BRB_DEV void plan_whole(const Md5Funnel<RW> &f, uint32_t b, Emit &p)
 {
     p.any = true;
     p.i0 = 0;
@@ -256,10 +258,10 @@ BRB_DEV void plan_whole(const brb_md5::FunnelT<RW> &f, uint32_t b, Emit &p)
 // addresses (3 instead of 4).  Whether any lane wraps is one ballot per half (wave-uniform branch);
 // with RW = 64 a whole half wraps in at most one of four consecutive halves.
 template <uint32_t RW, int H, bool WHOLE>
-BRB_DEV void emit_half(brb_md5::FunnelT<RW> &f, Emit &p, const uint32_t (&dw)[36])
+BRB_DEV void emit_half(Md5Funnel<RW> &f, Emit &p, const uint32_t (&dw)[36])
 {
     constexpr int lo = H ? 16 : -1, hi = H ? 32 : 16;
-    constexpr uint32_t M = brb_md5::FunnelT<RW>::kMask;
+    constexpr uint32_t M = Md5Funnel<RW>::kMask;
     // words written after this half: [i0, min(iw, hi)); the first slot after them (a whole line:
     // words 0 .. 31, so 16 after the first half and 32 after the second)
     const int top = p.iw < hi ? p.iw : hi;
@@ -273,8 +275,8 @@ BRB_DEV void emit_half(brb_md5::FunnelT<RW> &f, Emit &p, const uint32_t (&dw)[36
             const uint32_t base = f.ring | (f.lane4 + (s << 8));
 #pragma unroll
             for (int i = lo < 0 ? 0 : lo; i < hi; i++)
-                brb_md5::FunnelT<RW>::lds_st(base + uint32_t((i - (lo < 0 ? 0 : lo)) << 8),
-                                             __builtin_amdgcn_alignbit(dw[i + 1], dw[i], p.sh));
+                Md5Funnel<RW>::lds_st(base + uint32_t((i - (lo < 0 ? 0 : lo)) << 8),
+                                      __builtin_amdgcn_alignbit(dw[i + 1], dw[i], p.sh));
             f.wpos = p.wpos0 + n;
             return;
         }
@@ -289,10 +291,10 @@ BRB_DEV void emit_half(brb_md5::FunnelT<RW> &f, Emit &p, const uint32_t (&dw)[36
             const uint32_t v = __builtin_amdgcn_alignbit(dw[i + 1], dw[i < 0 ? 0 : i], p.sh);
             int a = abase + (i << 8);
             asm("v_med3_i32 %0, %1, %2, %3" : "=v"(a) : "v"(a), "v"(alo), "v"(ahi2));   // before i0 -> wpos0, past the range -> free slot
-            brb_md5::FunnelT<RW>::lds_st(uint32_t(a), v);
+            Md5Funnel<RW>::lds_st(uint32_t(a), v);
         }
         if (p.hmask && p.i0 >= lo && p.i0 < hi && p.i0 < p.iw)   // the head, over word i0's slot
-            brb_md5::FunnelT<RW>::lds_st(uint32_t(alo), p.head);
+            Md5Funnel<RW>::lds_st(uint32_t(alo), p.head);
         f.wpos = p.wpos0 + n;
         return;
     }
@@ -304,15 +306,15 @@ BRB_DEV void emit_half(brb_md5::FunnelT<RW> &f, Emit &p, const uint32_t (&dw)[36
         uint32_t a = p.abase + uint32_t(i << 8);
         if (!WHOLE)
             asm("v_med3_u32 %0, %1, %2, %3" : "=v"(a) : "v"(a), "v"(p.alo), "v"(ahi));   // before i0 -> wpos0, past the range -> free slot (alo <= ahi)
-        brb_md5::FunnelT<RW>::lds_st((a & M) | f.ring, v);
+        Md5Funnel<RW>::lds_st((a & M) | f.ring, v);
     }
     if (!WHOLE && p.hmask && p.i0 >= lo && p.i0 < hi && p.i0 < p.iw)   // the head, over word i0's slot
-        brb_md5::FunnelT<RW>::lds_st((p.alo & M) | f.ring, p.head);
+        Md5Funnel<RW>::lds_st((p.alo & M) | f.ring, p.head);
     f.wpos = p.wpos0 + n;
 }
 
 template <uint32_t RW>
-BRB_DEV void emit_finish(brb_md5::FunnelT<RW> &f, const Emit &p)
+BRB_DEV void emit_finish(Md5Funnel<RW> &f, const Emit &p)
 {
     if (p.ends) {
         f.nacc = p.rem;
@@ -345,7 +347,7 @@ BRB_DEV bool pc_room(uint32_t *cpx, uint32_t wpos, bool writes, uint64_t *idle =
 // Compresses every whole block waiting in the ring (one compress site per call; at most two blocks
 // wait after a half).
 template <uint32_t RW>
-BRB_DEV void pump_all(brb_md5::FunnelT<RW> &f)
+BRB_DEV void pump_all(Md5Funnel<RW> &f)
 {
     while (f.wpos - f.cpos >= 16)
         f.pump();
@@ -356,7 +358,7 @@ BRB_DEV void pump_all(brb_md5::FunnelT<RW> &f)
 // pair's ring (pc_room); after it, the word count posted to the consumer (wpx).  `writes`: this lane
 // has words in the line.  False when a wait timed out.
 template <uint32_t RW, bool WHOLE, bool PC>
-BRB_DEV bool emit_line(brb_md5::FunnelT<RW> &f, Emit &e, const uint32_t (&dw)[36], bool writes, uint32_t *cpx,
+BRB_DEV bool emit_line(Md5Funnel<RW> &f, Emit &e, const uint32_t (&dw)[36], bool writes, uint32_t *cpx,
                        uint32_t *wpx, uint64_t *idle = nullptr)
 {
     if (PC && !pc_room<RW>(cpx, f.wpos, writes, idle))
@@ -385,7 +387,7 @@ BRB_DEV bool emit_line(brb_md5::FunnelT<RW> &f, Emit &e, const uint32_t (&dw)[36
 // the producer stopped (2^22 sleeps with no word, no end and no beat of hb: a protocol fault; the
 // launch's digests are then wrong, but it ends, and the caller reports it: pair_fault.h).
 template <uint32_t RW>
-BRB_DEV bool pc_consume(brb_md5::FunnelT<RW> &f, uint32_t *ev_p, uint32_t end, uint32_t *wpx, uint32_t *cpx,
+BRB_DEV bool pc_consume(Md5Funnel<RW> &f, uint32_t *ev_p, uint32_t end, uint32_t *wpx, uint32_t *cpx,
                         uint32_t *hb, uint64_t *idle = nullptr)
 {
     uint32_t last = pc_beat_of(hb);

@@ -113,6 +113,13 @@ BRB_DEV void md5_compress(Md5State &st, const uint32_t (&m)[16])
     st.d += d;
 }
 
+// MD5 on 16 little-endian message words, as word_funnel.h takes an algorithm
+struct Md5Words {
+    using State = Md5State;
+    static BRB_DEV State iv() { return md5_iv(); }
+    static BRB_DEV void compress(State &st, uint32_t (&w)[16]) { md5_compress(st, w); }
+};
+
 // Padding blocks of a message whose last partial block holds `t` (< 64) bytes; `wtail` is that
 // partial block with the 0x80 marker already placed (tail_word_a4 / word_any).  Appends the
 // 64-bit bit length (md5.c:158-159: in[14] = bytes << 3, in[15] = bytes >> 29) and compresses

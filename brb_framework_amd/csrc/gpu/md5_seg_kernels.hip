@@ -5,33 +5,48 @@
 // concatenation, the items scattered in memory.  Batched: one record (one MetaData) per lane, its
 // segments (items) walked in order in 64-byte blocks (brb_io::BlockSrc, the next block in flight,
 // and the next segment's first block in flight while the current one is hashed), their bytes
-// funnelled into the lane's MD5 (md5_funnel.h).
+// funnelled into the lane's MD5 (word_funnel.h, seg_walk.h).
 #include "brb_kernels.h"
 #include "byte_stream.h"
 #include "digest_var_line.h"
 #include "line_stream.h"
-#include "md5_funnel.h"
+#include "seg_walk.h"
 #include "test_options.h"
 
 namespace {
 
 constexpr int kBlock = 256;
 
-// The per-lane block path: record r's segments read in 64-byte blocks (brb_io::BlockSrc, the next
-// block in flight, the next segment's first block in flight while the current one is hashed) and
-// funnelled into the lane's MD5.  Segment k is read as a range starting e_k = (bytes before it)
-// mod 4 bytes before it, so its words fall on the digest's word boundaries (Funnel::head); those e
-// bytes are the carried ones, never loaded from below the segment.  Used for groups whose lines span
-// 2 GiB or more, and by the round-3 kernel kept for A/B (test option seg_line = 0).
-template <uint32_t RW, class Beat = brb_line::NoBeat>
-BRB_DEV void seg_lane(brb_md5::FunnelT<RW> &f, const uint8_t *__restrict__ data, const uint64_t *__restrict__ soff,
-                      const uint32_t *__restrict__ slen, uint64_t k, uint64_t k1, Beat beat = Beat())
+// The per-lane block path: the MD5 of record segments [k, k1) through the shared walk (seg_walk.h),
+// per-lane block loads.  Used for groups whose lines span 2 GiB or more, and by the round-3 kernel
+// kept for A/B (test option seg_line = 0).
+template <uint32_t RW>
+BRB_DEV Md5State seg_digest(brb_funnel::Md5Funnel<RW> &f, const uint8_t *__restrict__ data,
+                            const uint64_t *__restrict__ soff, const uint32_t *__restrict__ slen, uint64_t k, uint64_t k1)
 {
-    uint64_t before = 0;
-    auto skip_empty = [&](uint64_t kk) {                // the next segment with bytes (an empty one's
-        while (kk < k1 && slen[kk] == 0) {              // address need not be memory); a beat per
-            kk++;                                       // skipped segment: a million-long run of empty
-            beat();                                     // ones outlasts the partner's idle budget
+    brb_line::NoBeat beat;
+    uint64_t total = 0;
+    brb_funnel::SegWalk w{data, soff, slen, k1};
+    w.first(k, 0, beat);
+    w.run<false>(f, beat, [&](uint32_t len) { total += len; });
+    return brb_funnel::md5_funnel_finish(f, total);
+}
+
+// The pair kernel's own per-lane walk, over the shared funnel and its block loop.  With seg_digest (the
+// shared walk) inlined into the producer, md5_seg_pc_kernel was 0.1 us slower on bench --op md5seg in
+// every interleaved A/B (parent 33.67, shared walk 33.81, the same with a 64-bit carry 33.81; with this
+// walk 33.64 against 33.71 and 33.71 against 33.77: profiles/r14/funnel_ab.json), so this one call site
+// keeps the walk it had: only the lengths are read while empty segments are skipped, a segment's offset
+// when it starts.
+template <uint32_t RW, class Beat>
+BRB_DEV Md5State seg_lane(brb_funnel::Md5Funnel<RW> &f, const uint8_t *__restrict__ data, const uint64_t *__restrict__ soff,
+                          const uint32_t *__restrict__ slen, uint64_t k, uint64_t k1, Beat beat)
+{
+    uint64_t before = 0, total = 0;
+    auto skip_empty = [&](uint64_t kk) {                // a beat per skipped segment, as SegWalk::find
+        while (kk < k1 && slen[kk] == 0) {
+            kk++;
+            beat();
         }
         return kk;
     };
@@ -41,27 +56,9 @@ BRB_DEV void seg_lane(brb_md5::FunnelT<RW> &f, const uint8_t *__restrict__ data,
         const uint32_t e = uint32_t(pre & 3);
         src.init(a - e, len + e, a);
     };
-    auto run = [&](brb_io::BlockSrc &src, uint64_t len) {   // 64-byte blocks, the next one in flight
-        const uint32_t e = f.nacc;
-        const uint64_t n = len + e;
-        for (uint64_t c = 0; c < n; c += 64) {
-            uint32_t w[16];
-            src.fetch(w);
-            if (c == 0)
-                w[0] = f.head(w[0]);
-            const uint64_t left = n - c;
-            if (left >= 64)
-                f.put16w(w);
-            else
-                f.put_tail(w, uint32_t(left));
-            f.pump();
-            beat();
-        }
-        if ((n & 63) == 0) {                            // ended on a whole block: nothing carried
-            f.acc = 0;
-            f.nacc = 0;
-        }
-        f.total += len;
+    auto run = [&](brb_io::BlockSrc &src, uint64_t len) {
+        f.template feed<false>(src, len, beat);
+        total += len;
     };
     brb_io::BlockSrc sa, sb;
     uint64_t la = 0, lb = 0;
@@ -82,6 +79,7 @@ BRB_DEV void seg_lane(brb_md5::FunnelT<RW> &f, const uint8_t *__restrict__ data,
         run(sb, lb);
         before += lb;
     }
+    return brb_funnel::md5_funnel_finish(f, total);
 }
 
 BRB_DEV void store_digest(uint8_t *out, uint64_t r, const Md5State &st)
@@ -97,15 +95,14 @@ __global__ __launch_bounds__(kBlock) void md5_seg_kernel(const uint8_t *__restri
                                                          const uint64_t *__restrict__ first, uint64_t n_rec,
                                                          uint8_t *__restrict__ out)
 {
-    __shared__ __attribute__((aligned(8192))) uint32_t blk[kBlock / 64][brb_md5::kRingWords][64];   // 8 KiB per wave
+    __shared__ __attribute__((aligned(8192))) uint32_t blk[kBlock / 64][brb_funnel::kRingWords][64];   // 8 KiB per wave
     const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const uint64_t r = uint64_t(blockIdx.x) * kBlock + threadIdx.x;
     if (r >= n_rec)
         return;
-    brb_md5::Funnel f;
+    brb_funnel::Md5Funnel<> f;
     f.init(&blk[wave][0][lane]);
-    seg_lane(f, data, soff, slen, first[r], first[r + 1]);
-    store_digest(out, r, f.finish());
+    store_digest(out, r, seg_digest(f, data, soff, slen, first[r], first[r + 1]));
 }
 
 // A group's segments in the wave's LDS table, and its line plan (both line-staged kernels).  The
@@ -222,14 +219,13 @@ __global__ __launch_bounds__(64 * W) void md5_seg_line_kernel(const uint8_t *__r
         const uint64_t rec = g * 64 + lane;
         const bool valid = rec < n_rec;
         const uint64_t k0 = valid ? first[rec] : 0, k1 = valid ? first[rec + 1] : 0;
-        brb_md5::FunnelT<RW> f;
+        brb_funnel::Md5Funnel<RW> f;
         f.init(&fring[wv][0][lane]);
+        uint64_t total = 0;                             // the record's bytes
         SegGroup<kTab> sg{tab_off[wv], tab_len[wv]};
         if (!sg.plan(soff, slen, k0, k1, valid, dbase, lane)) {   // the per-lane path
-            if (valid) {
-                seg_lane(f, data, soff, slen, k0, k1);
-                store_digest(out, rec, f.finish());
-            }
+            if (valid)
+                store_digest(out, rec, seg_digest(f, data, soff, slen, k0, k1));
             continue;
         }
         const uint32_t K = sg.K;
@@ -281,7 +277,7 @@ __global__ __launch_bounds__(64 * W) void md5_seg_line_kernel(const uint8_t *__r
             } else {
                 const bool fst = d.ss >= d.line;
                 if (has && fst)
-                    f.total += d.se - d.ss;
+                    total += d.se - d.ss;
                 plan_range(f, fst, d.ss - d.line, d.se - d.line < 4096u ? d.se - d.line : 4096u, b, e);
                 if (has)
                     edge_words(win, lds0 + sa, lds0 + sb, e);
@@ -336,7 +332,7 @@ __global__ __launch_bounds__(64 * W) void md5_seg_line_kernel(const uint8_t *__r
         continue;
 #endif
         if (valid)
-            store_digest(out, rec, f.finish());
+            store_digest(out, rec, brb_funnel::md5_funnel_finish(f, total));
     }
 }
 
@@ -409,7 +405,7 @@ __global__ __launch_bounds__(128 * NP) void md5_seg_pc_kernel(const uint8_t *__r
             pc_publish(&ev[pr][1], ++cev);              // plan read
             if (K == 0)
                 continue;                               // the producer runs this group alone
-            brb_md5::FunnelT<RW> f;
+            brb_funnel::Md5Funnel<RW> f;
             f.init(&fring[pr][0][lane]);
 #ifdef BRB_LINE_STAMPS
             if (!pc_consume(f, &ev[pr][0], pseen + 1, &wpx[pr][lane], &cpx[pr][lane], &ev[pr][3], &c_wait)) {
@@ -426,8 +422,8 @@ __global__ __launch_bounds__(128 * NP) void md5_seg_pc_kernel(const uint8_t *__r
             const uint32_t a = fin[pr][0][lane];
             f.acc = a & 0xFFFFFFu;
             f.nacc = a >> 24;
-            f.total = uint64_t(fin[pr][1][lane]) | (uint64_t(fin[pr][2][lane]) << 32);
-            const Md5State st = f.finish();
+            const Md5State st = brb_funnel::md5_funnel_finish(
+                f, uint64_t(fin[pr][1][lane]) | (uint64_t(fin[pr][2][lane]) << 32));
             pc_publish(&cpx[pr][lane], 0u);
             pc_publish(&ev[pr][1], ++cev);              // group done: ring, fin and cpos free
             const uint64_t rec = g * 64 + lane;
@@ -462,16 +458,15 @@ __global__ __launch_bounds__(128 * NP) void md5_seg_pc_kernel(const uint8_t *__r
         const uint64_t rec = g * 64 + lane;
         const bool valid = rec < n_rec;
         const uint64_t k0 = valid ? first[rec] : 0, k1 = valid ? first[rec + 1] : 0;
-        brb_md5::FunnelT<RW> f;
+        brb_funnel::Md5Funnel<RW> f;
         f.init(&fring[pr][0][lane]);
+        uint64_t total = 0;                             // the record's bytes
         auto alone = [&]() {                            // the per-lane path, this wave only
             ev[pr][2] = 0;
             pc_publish(&ev[pr][0], ++pev);
             cexp += 1;
-            if (valid) {
-                seg_lane(f, data, soff, slen, k0, k1, brb_line::HbBeat{&ev[pr][3], 0});
-                store_digest(out, rec, f.finish());
-            }
+            if (valid)
+                store_digest(out, rec, seg_lane(f, data, soff, slen, k0, k1, brb_line::HbBeat{&ev[pr][3], 0}));
         };
         SegGroup<kTab> sg{tab_off[pr], tab_len[pr]};
         if (!sg.plan(soff, slen, k0, k1, valid, dbase, lane)) {
@@ -519,7 +514,7 @@ __global__ __launch_bounds__(128 * NP) void md5_seg_pc_kernel(const uint8_t *__r
             } else {
                 const bool fst = d.ss >= d.line;
                 if (has && fst)
-                    f.total += d.se - d.ss;
+                    total += d.se - d.ss;
                 plan_range(f, fst, d.ss - d.line, d.se - d.line < 4096u ? d.se - d.line : 4096u, b, e);
                 if (has)
                     edge_words(win, lds0 + sa, lds0 + sb, e);
@@ -543,9 +538,9 @@ __global__ __launch_bounds__(128 * NP) void md5_seg_pc_kernel(const uint8_t *__r
         brb_dma::wait_vmcnt<0>();                       // the stray stage past K, before the slots are reused
         if (!ok)
             return;                                     // reported by the consumer (it stops getting words)
-        fin[pr][0][lane] = uint32_t(f.acc) | (f.nacc << 24);
-        fin[pr][1][lane] = uint32_t(f.total);
-        fin[pr][2][lane] = uint32_t(f.total >> 32);
+        fin[pr][0][lane] = f.acc | (f.nacc << 24);
+        fin[pr][1][lane] = uint32_t(total);
+        fin[pr][2][lane] = uint32_t(total >> 32);
         pc_publish(&ev[pr][0], ++pev);                  // the group's end
 #ifdef BRB_LINE_STAMPS
         if (lane == 0 && valid) {

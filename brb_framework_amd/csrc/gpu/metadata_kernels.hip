@@ -9,14 +9,14 @@
 // first item's fields in one read, an item's data streams in 64-byte blocks with the next block in
 // flight (brb_io::BlockSrc), and the 25 bytes after the data (the canary and the next item's
 // fields) are loaded before the data is hashed (Ahead).  The data feeds the lane's MD5
-// (md5_funnel.h).  The control flow and the
+// (word_funnel.h).  The control flow and the
 // unsigned-long arithmetic of cur_offset / cur_remaining / cur_needed are the reference's; see
 // include/brb_crypto.h for the two rules where the reference reads past its buffer.
 #include "brb_kernels.h"
 #include "byte_stream.h"
 #include "digest_var_line.h"
 #include "line_stream.h"
-#include "md5_funnel.h"
+#include "word_funnel.h"
 #include "test_options.h"
 
 namespace {
@@ -134,7 +134,7 @@ BRB_DEV uint32_t items_added(int32_t code, uint32_t items)
 // (test option seg_line = 0) is this function per lane.  `at`: the pack's offset in the caller's
 // data (the table's item offsets).
 template <uint32_t RW, class Beat = brb_line::NoBeat, class SinkT = Sink<>>
-BRB_DEV BRB_MetaDataUnpackInfo unpack_lane(brb_md5::FunnelT<RW> &f, const uint8_t *base, uint64_t size,
+BRB_DEV BRB_MetaDataUnpackInfo unpack_lane(brb_funnel::Md5Funnel<RW> &f, const uint8_t *base, uint64_t size,
                                            Beat beat = Beat(), const SinkT &sink = SinkT(), uint64_t r = 0,
                                            uint64_t at = 0)
 {
@@ -142,6 +142,7 @@ BRB_DEV BRB_MetaDataUnpackInfo unpack_lane(brb_md5::FunnelT<RW> &f, const uint8_
     int32_t code;
     uint32_t items = 0;
     uint64_t offset = 0, remaining = 0, needed = 0;   // cur_offset starts at the MemBuffer offset, 0
+    uint64_t total = 0;                               // bytes digested
 
     // MetaDataHeader (libbrb_data.h:322-330) and the first item's three fields: bytes 0 .. 87
     Ahead<22> hd;
@@ -178,30 +179,13 @@ BRB_DEV BRB_MetaDataUnpackInfo unpack_lane(brb_md5::FunnelT<RW> &f, const uint8_
             nx.issue(base, size, offset + sz);
             // The data is read from e = (bytes digested so far) mod 4 bytes before it (the item's
             // own fields, offset >= 88 > e), so its words fall on the digest's word boundaries: one
-            // funnel shift per word (in BlockSrc) and no carry shifting (md5_funnel.h put16w); the
+            // funnel shift per word (in BlockSrc) and no carry shifting (word_funnel.h put16w); the
             // first word's e low bytes are the carried ones.  Here sz + 1 <= size - offset.
             const uint32_t e = f.nacc;
-            const uint64_t n = sz + e;
             brb_io::BlockSrc bs;   // two blocks in flight (registers copied per block): 75.7 -> 81.4 us
-            bs.init(base + offset - e, n);
-            for (uint64_t c = 0; c < n; c += 64) {          // :249-254 BRB_MD5UpdateBig of the data
-                uint32_t w[16];
-                bs.fetch(w);
-                if (c == 0)
-                    w[0] = f.head(w[0]);
-                const uint64_t left = n - c;
-                if (left >= 64)
-                    f.put16w(w);
-                else
-                    f.put_tail(w, uint32_t(left));
-                f.pump();
-                beat();
-            }
-            if ((n & 63) == 0) {                            // ended on a whole block: nothing carried
-                f.acc = 0;
-                f.nacc = 0;
-            }
-            f.total += sz;
+            bs.init(base + offset - e, sz + e);
+            f.template feed<false>(bs, sz, beat);           // :249-254 BRB_MD5UpdateBig of the data
+            total += sz;
             offset += sz;
             remaining -= sz;
             if ((nx.dw(0) & 0xFFu) != 0x1Fu) {              // :258-268
@@ -224,7 +208,7 @@ BRB_DEV BRB_MetaDataUnpackInfo unpack_lane(brb_md5::FunnelT<RW> &f, const uint8_
             }
         }
         if (code == BRB_METADATA_UNPACK_SUCCESS) {          // :287-298
-            const Md5State st = f.finish();
+            const Md5State st = brb_funnel::md5_funnel_finish(f, total);
             if (st.a != dig[0] || st.b != dig[1] || st.c != dig[2] || st.d != dig[3])
                 code = BRB_METADATA_UNPACK_FAILED_DIGEST_INVALID;
         }
@@ -244,12 +228,12 @@ __global__ __launch_bounds__(kBlock) void metadata_unpack_kernel(const uint8_t *
                                                                  const uint32_t *__restrict__ lens, uint64_t n,
                                                                  BRB_MetaDataUnpackInfo *__restrict__ info)
 {
-    __shared__ __attribute__((aligned(8192))) uint32_t blk[kBlock / 64][brb_md5::kRingWords][64];   // 8 KiB per wave
+    __shared__ __attribute__((aligned(8192))) uint32_t blk[kBlock / 64][brb_funnel::kRingWords][64];   // 8 KiB per wave
     const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const uint64_t r = uint64_t(blockIdx.x) * kBlock + threadIdx.x;
     if (r >= n)
         return;
-    brb_md5::Funnel f;
+    brb_funnel::Md5Funnel<> f;
     f.init(&blk[wave][0][lane]);
     info[r] = unpack_lane(f, data + offs[r], lens[r]);
 }
@@ -260,13 +244,13 @@ __global__ __launch_bounds__(kBlock) void metadata_unpack_items_kernel(const uin
                                                                        const uint32_t *__restrict__ lens, uint64_t n,
                                                                        BRB_MetaDataUnpackInfo *__restrict__ info, Table tab)
 {
-    __shared__ __attribute__((aligned(8192))) uint32_t blk[kBlock / 64][brb_md5::kRingWords][64];
+    __shared__ __attribute__((aligned(8192))) uint32_t blk[kBlock / 64][brb_funnel::kRingWords][64];
     const Sink<Table> sink(tab);
     const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const uint64_t r = uint64_t(blockIdx.x) * kBlock + threadIdx.x;
     if (r >= n)
         return;
-    brb_md5::Funnel f;
+    brb_funnel::Md5Funnel<> f;
     f.init(&blk[wave][0][lane]);
     const uint64_t at = offs[r];
     info[r] = unpack_lane(f, data + at, lens[r], brb_line::NoBeat(), sink, r, sink.base() + at);
@@ -341,7 +325,7 @@ __global__ __launch_bounds__(64 * W * (PC ? 2 : 1)) void metadata_line_kernel(co
             pc_publish(&ev[pr][1], ++cev);              // plan read
             if (K == 0)
                 continue;                               // the producer runs this group alone
-            brb_md5::FunnelT<RW> f;
+            brb_funnel::Md5Funnel<RW> f;
             f.init(&fring[pr][0][lane]);
             if (!pc_consume(f, &ev[pr][0], pseen + 1, &wpx[pr][lane], &cpx[pr][lane], &ev[pr][3])) {
                 pc_fault_from(&fault_at);
@@ -354,10 +338,9 @@ __global__ __launch_bounds__(64 * W * (PC ? 2 : 1)) void metadata_line_kernel(co
                 v[q] = fin[pr][q][lane];
             f.acc = v[0] & 0xFFFFFFu;
             f.nacc = v[0] >> 24;
-            f.total = uint64_t(v[1]) | (uint64_t(v[2]) << 32);
             int32_t code = int32_t(v[3]);
             if (code == BRB_METADATA_UNPACK_SUCCESS) {  // :287-298
-                const Md5State st = f.finish();
+                const Md5State st = brb_funnel::md5_funnel_finish(f, uint64_t(v[1]) | (uint64_t(v[2]) << 32));
                 if (st.a != v[4] || st.b != v[5] || st.c != v[6] || st.d != v[7])
                     code = BRB_METADATA_UNPACK_FAILED_DIGEST_INVALID;
             }
@@ -402,7 +385,7 @@ __global__ __launch_bounds__(64 * W * (PC ? 2 : 1)) void metadata_line_kernel(co
         const uint64_t hi = brb_digest::uniform64(brb_digest::wave_max64(nl ? line0 + 128 * uint64_t(nl) : 0));
         const uint32_t Kl = __builtin_amdgcn_readfirstlane(uint32_t(brb_digest::wave_max64(nl)));
         const uint32_t K = Kl ? Kl : 1u;                  // iteration 1 reads every header
-        brb_md5::FunnelT<RW> f;
+        brb_funnel::Md5Funnel<RW> f;
         f.init(&fring[pr][0][lane]);
         if (!(hi > lo && hi - lo < (uint64_t(1) << 31) - (uint64_t(1) << 16))) {   // no line, or too wide
             if (PC) {                                     // the per-lane path, this wave only
@@ -417,6 +400,7 @@ __global__ __launch_bounds__(64 * W * (PC ? 2 : 1)) void metadata_line_kernel(co
                 else
                     info[r] = unpack_lane(f, reinterpret_cast<const uint8_t *>(base), size, brb_line::NoBeat(), sink, r, at);
             }
+            lane_path_done();
             continue;
         }
         if (PC) {
@@ -438,7 +422,7 @@ __global__ __launch_bounds__(64 * W * (PC ? 2 : 1)) void metadata_line_kernel(co
 
         int32_t code = BRB_METADATA_UNPACK_SUCCESS, item_count = 0, item = 0;
         uint32_t items = 0, phase = kDone, b = 0, dig[4] = {0, 0, 0, 0};
-        uint64_t offset = 0, remaining = 0, needed = 0, ds = 0, de = 0;
+        uint64_t offset = 0, remaining = 0, needed = 0, ds = 0, de = 0, total = 0;
         bool ok = true;
 
         // The walk's events whose first byte lies before pack byte L1, line k-1 = pack bytes [L0, L1)
@@ -499,7 +483,7 @@ __global__ __launch_bounds__(64 * W * (PC ? 2 : 1)) void metadata_line_kernel(co
                                 }
                                 ds = offset;
                                 de = offset + sz;
-                                f.total += sz;
+                                total += sz;
                                 offset += sz;                    // :249-256 (the walk's values after the data)
                                 remaining -= sz;
                                 phase = kData;
@@ -601,7 +585,7 @@ __global__ __launch_bounds__(64 * W * (PC ? 2 : 1)) void metadata_line_kernel(co
         if (valid)                                               // by the walking wave: the digest adds no item
             sink.done(r, items_added(code, items));
         if (PC) {
-            const uint32_t v[15] = {uint32_t(f.acc) | (f.nacc << 24), uint32_t(f.total), uint32_t(f.total >> 32),
+            const uint32_t v[15] = {f.acc | (f.nacc << 24), uint32_t(total), uint32_t(total >> 32),
                                     uint32_t(code), dig[0], dig[1], dig[2], dig[3], items,
                                     uint32_t(offset), uint32_t(offset >> 32), uint32_t(remaining),
                                     uint32_t(remaining >> 32), uint32_t(needed), uint32_t(needed >> 32)};
@@ -614,7 +598,7 @@ __global__ __launch_bounds__(64 * W * (PC ? 2 : 1)) void metadata_line_kernel(co
         if (!valid)
             continue;
         if (code == BRB_METADATA_UNPACK_SUCCESS) {               // :287-298
-            const Md5State st = f.finish();
+            const Md5State st = brb_funnel::md5_funnel_finish(f, total);
             if (st.a != dig[0] || st.b != dig[1] || st.c != dig[2] || st.d != dig[3])
                 code = BRB_METADATA_UNPACK_FAILED_DIGEST_INVALID;
         }

@@ -3,10 +3,10 @@
 // MetaDataPack (libbrb_core/data/utils/meta_data.c:104-140) writes a 64-byte header, then per item
 // {item_id, item_sub_id, sz; sz data bytes; 0x1F}; the header's digest (MetaDataHeaderLoadData,
 // :397-433) is BRB_MD5Init, one BRB_MD5UpdateBig per item, BRB_MD5Final.  Batched: one pack per lane.
-// A lane walks its items as md5_seg_kernels.hip::seg_lane does -- 64-byte blocks through
+// A lane walks its items as the segment walk (seg_walk.h) does -- 64-byte blocks through
 // brb_io::BlockSrc, the next block in flight, the next non-empty item's first block in flight while
 // the current one is hashed -- and every block it fetches has two consumers: the lane's MD5 funnel
-// (md5_funnel.h) and the pack's byte stream (PackSnk below).  So every item byte is loaded from HBM
+// (word_funnel.h) and the pack's byte stream (PackSnk below).  So every item byte is loaded from HBM
 // once.  The header goes out last, once the digest is known, through a brb_io::Snk (its start has any
 // alignment, and the pack before it may end in the same dword).
 //
@@ -21,7 +21,7 @@
 // doing (their item counts and lengths differ: nothing here assumes uniform control flow).
 #include "brb_kernels.h"
 #include "byte_stream.h"
-#include "md5_funnel.h"
+#include "word_funnel.h"
 
 namespace {
 
@@ -170,7 +170,7 @@ __global__ __launch_bounds__(kBlock) void metadata_pack_kernel(const uint8_t *__
                                                                const uint64_t *__restrict__ first, uint64_t n_packs,
                                                                uint8_t *out, const uint64_t *__restrict__ ooff)
 {
-    __shared__ __attribute__((aligned(8192))) uint32_t blk[kBlock / 64][brb_md5::kRingWords][64];   // 8 KiB per wave
+    __shared__ __attribute__((aligned(8192))) uint32_t blk[kBlock / 64][brb_funnel::kRingWords][64];   // 8 KiB per wave
     __shared__ __attribute__((aligned(16))) uint8_t rows[kBlock * PackSnk::kRowBytes];              // 9 KiB per wave
     const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const uint64_t r = uint64_t(blockIdx.x) * kBlock + threadIdx.x;
@@ -178,8 +178,9 @@ __global__ __launch_bounds__(kBlock) void metadata_pack_kernel(const uint8_t *__
         return;
     const uint64_t k0 = first[r], k1 = first[r + 1];
     uint64_t size = 0;                                  // MetaDataHeader.size: the body's bytes so far
+    uint64_t total = 0;                                 // bytes digested
     uint8_t *pack = out + ooff[r];
-    brb_md5::Funnel f;
+    brb_funnel::Md5Funnel<> f;
     f.init(&blk[wave][0][lane]);
     PackSnk snk;
     snk.init(pack + BRB_METADATA_HEADER_SIZE,
@@ -190,7 +191,7 @@ __global__ __launch_bounds__(kBlock) void metadata_pack_kernel(const uint8_t *__
             kk++;
         return kk;
     };
-    auto start = [&](brb_io::BlockSrc &src, uint64_t kk, uint64_t pre) {   // as seg_lane's
+    auto start = [&](brb_io::BlockSrc &src, uint64_t kk, uint64_t pre) {   // as SegWalk's
         const uint64_t len = ilen[kk];
         const uint8_t *a = data + ioff[kk];
         const uint32_t e = uint32_t(pre & 3);
@@ -252,11 +253,8 @@ __global__ __launch_bounds__(kBlock) void metadata_pack_kernel(const uint8_t *__
         }
         if (c >= n) {                                   // item k's last piece: its canary
             if (n) {
-                if ((n & 63) == 0) {                    // ended on a whole block: nothing carried
-                    f.acc = 0;
-                    f.nacc = 0;
-                }
-                f.total += len;
+                f.end_piece(n);
+                total += len;
                 before += len;
             }
             snk.put_byte(0x1F);
@@ -266,7 +264,7 @@ __global__ __launch_bounds__(kBlock) void metadata_pack_kernel(const uint8_t *__
         }
     }
     snk.finish();
-    const Md5State st = f.finish();
+    const Md5State st = brb_funnel::md5_funnel_finish(f, total);
     const uint32_t hw[16] = {0u, uint32_t(k1 - k0), uint32_t(size), uint32_t(size >> 32),
                              0x5F425242u, 0x4154454Du,   // "BRB_META"
                              st.a, st.b, st.c, st.d, 0u, 0u, 0u, 0u, 0u, 0u};

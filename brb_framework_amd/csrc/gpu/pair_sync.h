@@ -30,7 +30,7 @@ BRB_DEV uint32_t pc_beat_of(uint32_t *hb)
     return hb ? __builtin_amdgcn_readfirstlane(__hip_atomic_load(hb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) : 0u;
 }
 
-// Per-block beat hooks for code shared with the single-wave kernels (seg_lane, unpack_lane).
+// Per-block beat hooks for code shared with the single-wave kernels (SegWalk, Funnel::feed, unpack_lane).
 struct NoBeat {
     BRB_DEV void operator()() {}
 };
@@ -39,6 +39,20 @@ struct HbBeat {
     uint32_t n;
     BRB_DEV void operator()() { pc_beat(hb, ++n); }
 };
+
+// The end of a per-lane path inside a line-staged kernel's group loop: its last loads (BlockSrc keeps a
+// block in flight past the range's end) and stores are waited for here, vmcnt(0), where no LDS-DMA is in
+// flight.  Left pending across the loop's back edge, hipcc waits for them at the first reuse of a
+// register -- after the next group's first DMA issues, vmcnt(0) again, which then drains the DMA ring
+// before the loop's own counted wait (metadata_line_kernel: +2.6 % on bench --op metadata, seg_line 1;
+// the only user).  The builtin, not brb_dma::wait_vmcnt's inline assembly: hipcc's wait insertion must see
+// this wait to know that nothing is pending behind it.  gfx9 s_waitcnt encoding: vmcnt = bits 15:14 and
+// 3:0, expcnt = bits 6:4, lgkmcnt = bits 11:8; 0x0F70 is vmcnt(0) with expcnt and lgkmcnt at their maxima
+// (7, 15), i.e. not waited for -- as 0xC07F elsewhere in these kernels is lgkmcnt(0) alone.
+BRB_DEV void lane_path_done()
+{
+    __builtin_amdgcn_s_waitcnt(0x0F70);
+}
 
 // Waits until *ctr >= target; false after 2^22 sleeps without a beat of *hb (if given).
 BRB_DEV bool pc_wait_ge(uint32_t *ctr, uint32_t target, uint32_t *hb = nullptr)

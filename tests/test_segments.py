@@ -330,6 +330,119 @@ def test_segments_beyond_4gib(brb, torch_dev, seg_line):
     t.cuda.empty_cache()
 
 
+WALK_LENS = (0, 1, 3, 4, 5, 60, 63, 64, 65, 127, 128, 129)
+# segment lengths by record index mod 8; pattern 7 is 5, 0, 1 or 2 drawn lengths in turn
+WALK_PATTERNS = ((0, 0, 0),              # an all-empty list
+                 (0, 5, 64),             # empty first; carry 1 into the last
+                 (3, 0, 60),             # empty middle; carry 3 across it
+                 (65, 1, 0),             # empty last
+                 (1, 63, 128, 4),        # 1 carried + 63 = a whole block: the carry is reset; 128: again, none carried
+                 (5, 1, 129),            # carry 1, then carry 2
+                 (127, 3, 65, 64, 4))    # five segments: carry 3, 2, 3, 3
+
+
+def _walk_edges_case():
+    """130 records (two waves and two lanes), 0..5 segments each, segments at every offset residue mod 4."""
+    rng = np.random.default_rng(77)
+    n = 130
+    lists = []
+    for r in range(n):
+        p = r % 8
+        if p < 7:
+            lists.append(list(WALK_PATTERNS[p]))
+        else:
+            lists.append([int(x) for x in rng.choice(WALK_LENS, (5, 0, 1, 2)[(r // 8) % 4])])
+    first = np.zeros(n + 1, np.uint64)
+    first[1:] = np.cumsum([len(s) for s in lists])
+    lens = np.array([m for s in lists for m in s], np.uint32)
+    pool = workload.gen_records(0x5EED00FD, 0, 1, 1 << 16)
+    offs = np.zeros(lens.size, np.uint64)
+    for r in range(n):
+        for j, k in enumerate(range(int(first[r]), int(first[r + 1]))):
+            offs[k] = 4 * int(rng.integers(1, (1 << 14) - 64)) + (r + j) % 4
+    return pool, offs, lens, first, lists
+
+
+def _walk_edges_present(lists, offs, lens):
+    """The cases the shared walk must meet, found in the generated lists themselves."""
+    seen = set()
+    for s in lists:
+        full = [j for j, m in enumerate(s) if m]
+        if s and not full:
+            seen.add("all empty")
+        if full and s[0] == 0:
+            seen.add("empty first")
+        if full and s[-1] == 0:
+            seen.add("empty last")
+        if any(m == 0 and full and full[0] < j < full[-1] for j, m in enumerate(s)):
+            seen.add("empty middle")
+        before = 0
+        for j, m in enumerate(s):
+            if m and j < (full[-1] if full else 0):       # a piece with bytes, and another one after it
+                e = before % 4
+                if (m + e) % 64 == 0:
+                    seen.add("block end, then a piece")
+                    if e:
+                        seen.add("block end with carried bytes, then a piece")
+                if (before + m) % 4:
+                    seen.add(f"carry {(before + m) % 4}")
+            before += m
+    seen |= {f"offset residue {int(o) % 4}" for o, m in zip(offs, lens) if m}
+    seen |= {f"length {int(m)}" for m in lens}
+    return seen
+
+
+def test_walk_edges_all_routes(brb, torch_dev):
+    """One set of segment lists through every caller of the shared segment walk (seg_walk.h), all equal to
+    hashlib: BRB_MD5BatchSegments with seg_line 0 / 1 / 2 (per-lane kernel, line kernel, wave pairs); the same
+    lists with one record of each 64-record group moved 2 GiB away, so that every group takes the per-lane
+    fallback inside the line and pair kernels; and Init + UpdateSegmentsBatch(final = 1) on fresh MD5 and
+    SHA-1 contexts."""
+    t = torch_dev
+    pool, offs, lens, first, lists = _walk_edges_case()
+    n = len(lists)
+    want_cases = {"all empty", "empty first", "empty middle", "empty last", "block end, then a piece",
+                  "block end with carried bytes, then a piece", "carry 1", "carry 2", "carry 3"}
+    want_cases |= {f"offset residue {q}" for q in range(4)} | {f"length {m}" for m in WALK_LENS}
+    assert want_cases <= _walk_edges_present(lists, offs, lens)
+    assert {len(s) for s in lists} == set(range(6))
+    msgs = [b"".join(pool[int(offs[k]):int(offs[k]) + int(lens[k])].tobytes()
+                     for k in range(int(first[i]), int(first[i + 1]))) for i in range(n)]
+    want = {alg: np.frombuffer(b"".join(getattr(hashlib, alg)(m).digest() for m in msgs), np.uint8).reshape(n, -1)
+            for alg in ("md5", "sha1")}
+
+    dev = lambda a: t.from_numpy(np.ascontiguousarray(a)).cuda()   # noqa: E731
+    d, o, ln, fi = dev(pool), dev(offs), dev(lens), dev(first)
+    for seg_line in (0, 1, 2):
+        with brb.TestOption("seg_line", seg_line):
+            got = brb.md5_batch_segments(d, o, ln, fi).cpu().numpy()
+        assert np.array_equal(got, want["md5"]), seg_line
+
+    far = (1 << 31) + 4096                       # keeps every offset's residue mod 4
+    wide = t.empty(far + pool.size, dtype=t.uint8, device="cuda")
+    wide[: pool.size] = d
+    wide[far:] = d
+    offs_w = offs.copy()
+    for r in (4, 68, 129):                       # one record with bytes in each group
+        assert any(lists[r])
+        offs_w[int(first[r]):int(first[r + 1])] += np.uint64(far)
+    ow = dev(offs_w)
+    for seg_line in (1, 2):
+        with brb.TestOption("seg_line", seg_line):
+            got = brb.md5_batch_segments(wide, ow, ln, fi).cpu().numpy()
+        assert np.array_equal(got, want["md5"]), seg_line
+    del wide
+    t.cuda.empty_cache()
+
+    o64, l32, f64 = dev(offs.view(np.int64)), dev(lens.view(np.int32)), dev(first.view(np.int64))
+    fin = dev(np.ones(n, np.uint8))
+    for alg, width in (("md5", 168), ("sha1", 92)):
+        ctxs = t.zeros((n, width), dtype=t.uint8, device="cuda")
+        getattr(brb, alg + "_init_batch")(ctxs)
+        got = getattr(brb, alg + "_update_segments_batch")(ctxs, d, o64, l32, f64, final=fin).cpu().numpy()
+        assert np.array_equal(got, want[alg]), alg
+
+
 @pytest.mark.parametrize("device", [False, True])
 def test_segments_pair_fault_reported(brb, torch_dev, device):
     """A protocol fault in the producer / consumer pair (test option pair_stall: the first pair never
