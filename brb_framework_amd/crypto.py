@@ -182,6 +182,7 @@ _SIGNATURES = [
      [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int, ctypes.POINTER(BRB_RC4_State)]),
     ("BRB_TransformBatcherInjectFault", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     ("BRB_CryptoGPU_TestOption", ctypes.c_int, [ctypes.c_char_p, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]),
+    ("BRB_CryptoGPU_TestFixedRoute", ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint32]),
     ("BRB_CryptoGPU_HostRegister", ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64]),
     ("BRB_CryptoGPU_HostUnregister", ctypes.c_int, [ctypes.c_void_p]),
     ("BRB_CryptoGPU_Available", ctypes.c_int, []),
@@ -268,6 +269,17 @@ class TestOption:
     def __exit__(self, *exc):
         test_option(self.name, self.old)
         return False
+
+
+# BRB_FIXED_ROUTE_* (include/brb_crypto.h), in launch order
+(FIXED_ROUTE_LANE_A4, FIXED_ROUTE_LANE_ANY, FIXED_ROUTE_LINE, FIXED_ROUTE_VAR_LINE, FIXED_ROUTE_DMA_TICKET,
+ FIXED_ROUTE_B64R_8, FIXED_ROUTE_B64R_4, FIXED_ROUTE_B64, FIXED_ROUTE_DMA_SHORT) = range(9)
+
+
+def fixed_route(addr: int, rec_len: int) -> int:
+    """BRB_CryptoGPU_TestFixedRoute: the FIXED_ROUTE_* kernel choice of a fixed-stride digest call for
+    records of rec_len bytes at address addr, under the current test options (no device needed)."""
+    return lib().BRB_CryptoGPU_TestFixedRoute(int(addr), int(rec_len))
 
 
 def _check(rc: int, what: str) -> None:

@@ -14,6 +14,7 @@
 
 #include "brb_crypto.h"
 #include "api_util.h"
+#include "fixed_route.h"
 #include "host_pipe.h"
 #include "pair_fault.h"
 #include "test_options.h"
@@ -344,6 +345,11 @@ int BRB_CryptoGPU_TestOption(const char *name, int value, int *old)
         }
     set_err("unknown test option '%s'", name);
     return BRB_BATCH_BADARG;
+}
+
+int BRB_CryptoGPU_TestFixedRoute(uint64_t data_addr, uint32_t rec_len)
+{
+    return brb_digest::fixed_route(uintptr_t(data_addr), rec_len);
 }
 
 }  // extern "C"

@@ -13,6 +13,7 @@
 #include "digest_line.h"
 #include "digest_var_line.h"
 #include "dma_stage.h"
+#include "fixed_route.h"
 
 namespace brb_digest {
 
@@ -303,22 +304,11 @@ __global__ __launch_bounds__(64 * WAVES) void digest_b64r_kernel(const uint8_t *
         Alg::template store<OUT_ALIGNED>(out, rprev, prev);
 }
 
-// Host-side launch.
-inline bool dma_supported(uint32_t rec_len)
-{
-    return rec_len > 0 && uint64_t(rec_len) * 64 + 64 < (uint64_t(1) << 31);
-}
-
-// Test option "fixed_var_line" = 0 keeps byte-aligned fixed-stride records on the record-relative
-// kernel (A/B measurements).
-inline bool fixed_var_line_enabled()
-{
-    return brb_opt::get(brb_opt::kFixedVarLine) != 0;
-}
-
+// Host-side launch of the LDS-DMA routes: `route` is fixed_route's choice for (data, rec_len)
+// (fixed_route.h); the two per-lane routes belong to the callers (md5_kernels.hip, sha1_kernels.hip).
 template <class Alg>
-hipError_t launch_fixed_dma(const uint8_t *data, uint32_t rec_len, uint64_t n_rec, uint8_t *out, bool out_al,
-                            hipStream_t s)
+hipError_t launch_fixed_dma(FixedRoute route, const uint8_t *data, uint32_t rec_len, uint64_t n_rec, uint8_t *out,
+                            bool out_al, hipStream_t s)
 {
     // Shapes measured with tools/mb/md5_ab.hip (interleaved, one process):
     //  * records > 64 B at any alignment: 128-byte stages, ring of 2 (16 KiB per wave): 1 Mi x
@@ -328,14 +318,15 @@ hipError_t launch_fixed_dma(const uint8_t *data, uint32_t rec_len, uint64_t n_re
     constexpr int W = 4;
     const uint64_t groups = (n_rec + 63) / 64;
     const uint64_t wgs_needed = (groups + W - 1) / W;
-    // 4-byte record bases and lengths over 64 B: line-aligned staging, digest_line.h (every line
-    // is read once; no 128-byte piece straddles two lines).  1 Mi x 1500 B: 343 -> 300 us,
-    // cfg2: 25.3 -> 24.9 us (tools/mb/md5_ab.hip).
-    if (line_supported(data, rec_len))
+    switch (route) {
+    case kRouteLine:
+        // 4-byte record bases and lengths over 64 B: line-aligned staging, digest_line.h (every line
+        // is read once; no 128-byte piece straddles two lines).  1 Mi x 1500 B: 343 -> 300 us,
+        // cfg2: 25.3 -> 24.9 us (tools/mb/md5_ab.hip).
         return launch_fixed_line<Alg>(data, rec_len, n_rec, out, out_al, s);
-    if (rec_len > 64 && rec_len <= (1u << 20) && fixed_var_line_enabled())
+    case kRouteVarLine:
         return launch_fixed_var_line<Alg>(data, rec_len, n_rec, out, out_al, s);   // any byte alignment
-    if (rec_len > 64) {
+    case kRouteDmaTicket: {
         // one 8-wave workgroup per CU (two waves per SIMD, 128 KiB of LDS), persistent, groups
         // handed out by tickets, 128-byte stages, ring of 2
         const unsigned g = unsigned(groups < device_cu_count() ? groups : device_cu_count());
@@ -343,23 +334,30 @@ hipError_t launch_fixed_dma(const uint8_t *data, uint32_t rec_len, uint64_t n_re
             digest_fixed_dma_kernel<Alg, 8, 2, 2, true, false, true><<<g, 512, 0, s>>>(data, rec_len, n_rec, out);
         else
             digest_fixed_dma_kernel<Alg, 8, 2, 2, false, false, true><<<g, 512, 0, s>>>(data, rec_len, n_rec, out);
-    } else if (rec_len == 64 && brb_opt::get(brb_opt::kB64Kernel) >= 2) {
-        // register-buffered 64-byte kernel: 16 KiB per workgroup; option 2: 8 workgroups per CU
-        // (8 waves per SIMD), option 3: 4 per CU
-        const unsigned cap = brb_opt::get(brb_opt::kB64Kernel) == 2 ? 2048u : 1024u;
+        break;
+    }
+    case kRouteB64R8:
+    case kRouteB64R4: {
+        // register-buffered 64-byte kernel: 16 KiB per workgroup; 8 workgroups per CU (8 waves per
+        // SIMD) or 4 per CU
+        const unsigned cap = route == kRouteB64R8 ? 2048u : 1024u;
         const unsigned g = unsigned(wgs_needed < cap ? wgs_needed : cap);
         if (out_al)
             digest_b64r_kernel<Alg, W, true><<<g, 64 * W, 0, s>>>(data, n_rec, out);
         else
             digest_b64r_kernel<Alg, W, false><<<g, 64 * W, 0, s>>>(data, n_rec, out);
-    } else if (rec_len == 64 && brb_opt::get(brb_opt::kB64Kernel) != 0) {
+        break;
+    }
+    case kRouteB64: {
         // the lean 64-byte kernel, same shape as below (4 workgroups of 4 waves per CU, 32 KiB each)
         const unsigned g = unsigned(wgs_needed < 1024 ? wgs_needed : 1024);
         if (out_al)
             digest_b64_kernel<Alg, W, true><<<g, 64 * W, 0, s>>>(data, n_rec, out);
         else
             digest_b64_kernel<Alg, W, false><<<g, 64 * W, 0, s>>>(data, n_rec, out);
-    } else {
+        break;
+    }
+    case kRouteDmaShort: {
         // 4 workgroups per CU (32 KiB each), static groups: 1 Mi x 64 B = 16 384 groups = exactly 4
         // per wave.  Measured (md5_ab, 1 Mi x 64 B): 24.6 us; one 16-wave workgroup per CU with
         // tickets 25.3 us; a ring of 3 at 3 workgroups per CU 26.1 us.
@@ -368,6 +366,10 @@ hipError_t launch_fixed_dma(const uint8_t *data, uint32_t rec_len, uint64_t n_re
             digest_fixed_dma_kernel<Alg, W, 2, 1, true><<<g, 64 * W, 0, s>>>(data, rec_len, n_rec, out);
         else
             digest_fixed_dma_kernel<Alg, W, 2, 1, false><<<g, 64 * W, 0, s>>>(data, rec_len, n_rec, out);
+        break;
+    }
+    default:                                       // the per-lane routes are not launched here
+        return hipErrorInvalidValue;
     }
     return hipGetLastError();
 }

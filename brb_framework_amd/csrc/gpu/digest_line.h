@@ -326,12 +326,6 @@ __global__ __launch_bounds__(64 * WAVES, 2) void digest_line_kernel(const uint8_
     BRB_LINE_PROBE(3);
 }
 
-// Line-aligned staging needs 4-byte record bases (the window shift is whole dwords).
-inline bool line_supported(const uint8_t *data, uint32_t rec_len)
-{
-    return rec_len > 64 && rec_len <= (1u << 20) && (rec_len & 3) == 0 && (reinterpret_cast<uintptr_t>(data) & 3) == 0;
-}
-
 inline unsigned device_cu_count()
 {
     static const unsigned n = [] {

@@ -125,22 +125,24 @@ hipError_t launch_sha1_fixed(const uint8_t *data, uint32_t rec_len, uint64_t n_r
     if (n_rec == 0)
         return hipSuccess;
     const bool out_al = (reinterpret_cast<uintptr_t>(out) & 3) == 0;
-    const bool in_a4 = (reinterpret_cast<uintptr_t>(data) & 3) == 0 && (rec_len & 3) == 0;
     const unsigned g = grid_for(n_rec);
-    if (brb_digest::dma_supported(rec_len))
-        return brb_digest::launch_fixed_dma<Sha1Alg>(data, rec_len, n_rec, out, out_al, s);
-    if (in_a4) {
+    const brb_digest::FixedRoute route = brb_digest::fixed_route(reinterpret_cast<uintptr_t>(data), rec_len);
+    switch (route) {
+    case brb_digest::kRouteLaneA4:
         if (out_al)
             sha1_fixed_a4_kernel<kBlock, true><<<g, kBlock, 0, s>>>(data, rec_len, n_rec, out);
         else
             sha1_fixed_a4_kernel<kBlock, false><<<g, kBlock, 0, s>>>(data, rec_len, n_rec, out);
-    } else {
+        return hipGetLastError();
+    case brb_digest::kRouteLaneAny:
         if (out_al)
             sha1_any_kernel<kBlock, true, true><<<g, kBlock, 0, s>>>(data, nullptr, nullptr, rec_len, n_rec, out);
         else
             sha1_any_kernel<kBlock, true, false><<<g, kBlock, 0, s>>>(data, nullptr, nullptr, rec_len, n_rec, out);
+        return hipGetLastError();
+    default:
+        return brb_digest::launch_fixed_dma<Sha1Alg>(route, data, rec_len, n_rec, out, out_al, s);
     }
-    return hipGetLastError();
 }
 
 hipError_t launch_sha1_var(const uint8_t *data, const uint64_t *offs, const uint32_t *lens, uint64_t n_rec,

@@ -672,6 +672,30 @@ int BRB_CryptoGPU_HostUnregister(void *p);
  * block per lane).  Returns 1 and the previous
  * value in *old (if not NULL), or -1 for an unknown name or a value out of range. */
 int BRB_CryptoGPU_TestOption(const char *name, int value, int *old);
+/* Test support, not for production use: the kernel that BRB_MD5BatchFixed / BrbSha1_BatchFixed run
+ * in device mode for records of rec_len bytes whose first byte is at address data_addr, under the
+ * current values of the test options "fixed_var_line" and "b64_kernel".  It is the launchers' own
+ * routing function, so it is the source of truth for which shape reaches which kernel; it needs no
+ * device and touches no memory.  Returns one of BRB_FIXED_ROUTE_* (in launch order):
+ *   LANE_A4    rec_len == 0 or rec_len >= 33 554 431 (64 rec_len + 64 >= 2^31), base and length
+ *              4-byte multiples: md5_ / sha1_fixed_a4_kernel, one record per lane
+ *   LANE_ANY   the same lengths otherwise: md5_ / sha1_any_kernel, one record per lane
+ *   LINE       64 < rec_len <= 1 MiB, base and length 4-byte multiples: digest_line_kernel
+ *   VAR_LINE   64 < rec_len <= 1 MiB otherwise, "fixed_var_line" 1: digest_var_line_kernel
+ *   DMA_TICKET every other rec_len > 64: digest_fixed_dma_kernel, groups handed out by tickets
+ *   B64R_8, B64R_4, B64   rec_len == 64 under "b64_kernel" 2, 3, 1: digest_b64r_kernel at a grid
+ *              cap of 2048 / 1024 workgroups, digest_b64_kernel
+ *   DMA_SHORT  1 <= rec_len <= 64 otherwise: digest_fixed_dma_kernel with 64-byte stages */
+#define BRB_FIXED_ROUTE_LANE_A4    0
+#define BRB_FIXED_ROUTE_LANE_ANY   1
+#define BRB_FIXED_ROUTE_LINE       2
+#define BRB_FIXED_ROUTE_VAR_LINE   3
+#define BRB_FIXED_ROUTE_DMA_TICKET 4
+#define BRB_FIXED_ROUTE_B64R_8     5
+#define BRB_FIXED_ROUTE_B64R_4     6
+#define BRB_FIXED_ROUTE_B64        7
+#define BRB_FIXED_ROUTE_DMA_SHORT  8
+int BRB_CryptoGPU_TestFixedRoute(uint64_t data_addr, uint32_t rec_len);
 /* Library version string. */
 const char *BRB_CryptoGPU_Version(void);
 

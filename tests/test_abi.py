@@ -32,6 +32,7 @@ def test_header_declares_reference_symbols():
     assert reference <= fns
     assert {"BRB_MD5BatchFixed", "BRB_MD5Batch", "BrbSha1_BatchFixed", "BrbSha1_Batch",
             "BRB_Blowfish_EncryptBatch", "BRB_Blowfish_DecryptBatch"} <= fns
+    assert {"BRB_CryptoGPU_TestOption", "BRB_CryptoGPU_TestFixedRoute"} <= fns       # test support
 
 
 def test_library_exports_exactly_the_header(brb):

@@ -64,7 +64,7 @@ P1500, P1499, P64, P20, PBIG = (per_chunk(x) for x in (1500, 1499, 64, 20, 1_200
 HOST_DIGEST_CASES = [
     (1500, 3 * P1500 + 1, None),       # three full chunks and a last chunk of one record
     (1500, 2 * P1500, None),           # exact multiple: the last chunk is full
-    (1499, 4 * P1499 + 5, None),       # chunk bases 0..3 mod 4 (record-relative kernel)
+    (1499, 4 * P1499 + 5, None),       # chunk bases 0..3 mod 4 (fixed_route VAR_LINE: the var-line kernel)
     (64, 2 * P64 + 65, 2),             # the 64-byte kernels at a chunk edge
     (64, 2 * P64 + 65, 1),
     (20, 2 * P20 + 1, None),

@@ -173,6 +173,18 @@ def test_group_and_lane_edges(brb, orc, torch_dev, keyset, n_rec, mode):
     _three_way(brb, orc, torch_dev, keyset, woff, total, cnt, None, keyset[2][:n_rec], mode, 100 + n_rec)
 
 
+@pytest.mark.gpu
+@pytest.mark.parametrize("bf_keyed", [1, 2])
+@pytest.mark.parametrize("n_rec", N_RECS)
+def test_group_and_lane_edges_kernel_variants(brb, orc, torch_dev, keyset, n_rec, bf_keyed):
+    """The same shapes on the other two forms of the keyed kernel (test option bf_keyed: 1 the plain
+    image fill, 2 one block per lane; 0, the default, runs above), device mode, encrypt and decrypt."""
+    cnt = edge_counts(n_rec)
+    woff, total = layout(cnt, n_rec)
+    with brb.TestOption("bf_keyed", bf_keyed):
+        _three_way(brb, orc, torch_dev, keyset, woff, total, cnt, None, keyset[2][:n_rec], "device", 100 + n_rec)
+
+
 # ---- placement ---------------------------------------------------------------------------------------
 @pytest.mark.gpu
 @pytest.mark.parametrize("mode", ["device", "host"])

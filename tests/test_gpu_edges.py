@@ -1,7 +1,10 @@
 """GPU parity at the edges of the digest and Blowfish batch paths (SURVEY §8(a), §7 edge cases):
-empty batches, records on both sides of the line kernel's 1 MiB limit (digest_line.h
-`line_supported`), and batches whose bytes run past 4 GiB (64-bit record addressing in the buffer
-descriptors).  The oracle, or hashlib where the oracle would take minutes, is the checker.
+empty batches, records on both sides of the line kernel's 1 MiB limit (fixed_route.h
+`line_supported`: past it fixed_route gives DMA_TICKET, the record-relative ticketed kernel of
+digest_dma.h), and batches whose bytes run past 4 GiB (64-bit record addressing in the buffer
+descriptors: fixed_route LINE for 65 540 B records, VAR_LINE for 65 538 B ones).  The oracle, or hashlib
+where the oracle would take minutes, is the checker.  Which shape reaches which kernel is pinned by
+tests/test_digest_routes.py through BRB_CryptoGPU_TestFixedRoute.
 """
 import hashlib
 
@@ -61,8 +64,9 @@ def test_records_around_line_limit(brb, orc, torch_dev, rec_len):
 
 @pytest.mark.parametrize("rec_len", [65540, 65538])
 def test_batch_past_4gib(brb, torch_dev, rec_len):
-    """65 600 records of ~64 KiB = 4.3 GB: record bases past 2^32 in the line kernel (65 540 B) and
-    the record-relative one (65 538 B).  Device-mode digests of every record equal the host-mode
+    """65 600 records of ~64 KiB = 4.3 GB: record bases past 2^32 in the line kernel (65 540 B,
+    fixed_route LINE) and in the var-line kernel's fixed-stride form (65 538 B: 2 mod 4, fixed_route
+    VAR_LINE).  Device-mode digests of every record equal the host-mode
     (chunked pipeline) ones; 96 records, the ones around the 4 GiB boundary and the last included,
     equal hashlib."""
     torch = torch_dev

@@ -76,7 +76,7 @@ def test_unaligned_output(brb, orc, torch_dev):
     assert np.array_equal(o1.cpu().numpy(), orc.sha1_batch_fixed(data.cpu().numpy(), L, n))
 
 
-def test_variable_records(brb, orc, torch_dev):
+def _variable_records_case():
     rng = np.random.default_rng(11)
     n = 3000
     buf = workload.gen_records(0x5EED0005, 0, 1, 1 << 20)
@@ -84,6 +84,10 @@ def test_variable_records(brb, orc, torch_dev):
     lens[:50] = 0
     lens[50:100] = rng.choice([55, 56, 63, 64, 65, 119, 120], 50)
     offs = rng.integers(0, buf.size - 4000, n).astype(np.uint64)      # overlapping, any alignment
+    return buf, offs, lens
+
+
+def _check_variable_records(brb, orc, torch_dev, buf, offs, lens):
     want5, want1 = orc.md5_batch(buf, offs, lens), orc.sha1_batch(buf, offs, lens)
     # host mode
     assert np.array_equal(brb.md5_batch(buf, offs, lens), want5)
@@ -92,6 +96,38 @@ def test_variable_records(brb, orc, torch_dev):
     d, o, ln = to_dev(torch_dev, buf), to_dev(torch_dev, offs.view(np.int64)), to_dev(torch_dev, lens.view(np.int32))
     assert np.array_equal(brb.md5_batch(d, o, ln).cpu().numpy(), want5)
     assert np.array_equal(brb.sha1_batch(d, o, ln).cpu().numpy(), want1)
+
+
+def test_variable_records(brb, orc, torch_dev):
+    _check_variable_records(brb, orc, torch_dev, *_variable_records_case())
+
+
+def test_variable_records_per_lane_kernel(brb, orc, torch_dev):
+    """The same batch under test option var_line = 0: md5_ / sha1_any_kernel<FIXED = false> on records
+    of up to 4 000 bytes at any alignment, overlapping, with empty ones."""
+    with brb.TestOption("var_line", 0):
+        _check_variable_records(brb, orc, torch_dev, *_variable_records_case())
+
+
+VAR_LONG_LENS = (0, 1, 65_537, (1 << 20) - 1, 1 << 20, (1 << 20) + 1, (3 << 20) + 61)
+
+
+def test_variable_records_long(brb, torch_dev):
+    """130 records (two full groups and a partial one) whose lengths cycle through 0, 1, 64 KiB + 1,
+    1 MiB - 1, 1 MiB, 1 MiB + 1 and 3 MiB + 61, at random byte offsets in an 8 MiB pool (overlapping,
+    every alignment): BRB_MD5Batch and BrbSha1_Batch in device mode against hashlib."""
+    rng = np.random.default_rng(21)
+    n, pool = 130, 8 << 20
+    buf = rng.integers(0, 256, pool, dtype=np.uint8)
+    lens = np.array([VAR_LONG_LENS[i % len(VAR_LONG_LENS)] for i in range(n)], np.uint32)
+    offs = np.array([rng.integers(0, pool - int(k) + 1) for k in lens], np.uint64)
+    assert {int(o) & 3 for o in offs} == {0, 1, 2, 3} and int((offs + lens).max()) <= pool
+    recs = [buf[int(o):int(o) + int(k)].tobytes() for o, k in zip(offs, lens)]
+    d, o, ln = to_dev(torch_dev, buf), to_dev(torch_dev, offs.view(np.int64)), to_dev(torch_dev, lens.view(np.int32))
+    got5, got1 = brb.md5_batch(d, o, ln).cpu().numpy(), brb.sha1_batch(d, o, ln).cpu().numpy()
+    for i, rec in enumerate(recs):
+        assert got5[i].tobytes() == hashlib.md5(rec).digest(), f"md5 record {i} of {lens[i]} bytes"
+        assert got1[i].tobytes() == hashlib.sha1(rec).digest(), f"sha1 record {i} of {lens[i]} bytes"
 
 
 def test_cfg2_full(brb, orc, torch_dev, golden):
@@ -127,7 +163,7 @@ def test_cfg3_full(brb, orc, torch_dev, golden):
     (65600, 1504, 0),        # even dword stride
     (5000, 160, 4),          # smallest length with four DMAs per M0 write (instruction offsets)
     (5000, 156, 8),          # largest length without
-    (3000, 1501, 0),         # not 4-byte multiple: record-relative stages (digest_dma.h), tickets
+    (3000, 1501, 0),         # not a 4-byte multiple: the var-line kernel's fixed-stride form (fixed_route: VAR_LINE)
 ])
 def test_large_batch_staging(brb, orc, torch_dev, n, rec_len, off):
     data = workload.gen_records(0x5EED0006, 0, n, rec_len)
@@ -254,7 +290,9 @@ def test_line_kernel_parities(brb, orc, torch_dev, rec_len, off):
 def test_many_groups_per_wave(brb, orc, torch_dev, rec_len):
     """Batches large enough that every wave takes several 64-record groups from its workgroup's
     ticket counter (300 000 records = 4 688 groups over 2 048 wave slots): the line-staged kernel
-    (1500 B) and the record-relative one (1501 B), every digest against the oracle."""
+    (1500 B, fixed_route LINE) and the var-line kernel's fixed-stride form (1501 B, fixed_route
+    VAR_LINE; the record-relative ticketed kernel is run by test_digest_routes.py), every digest
+    against the oracle."""
     n = 300_000
     data = workload.gen_records(0x5EED0005, 0, n, rec_len)
     d = to_dev(torch_dev, data)

@@ -1,6 +1,7 @@
 """Streaming MD5 / SHA-1 contexts as a batch on the GPU (BRB_MD5InitBatch / UpdateBatch / FinalBatch and the
 BrbSha1_ three), byte for byte against the product's own compat functions (pinned by test_compat.py) and
-against hashlib.  Every case is tiny: a few hundred contexts, pieces of at most a few hundred bytes."""
+against hashlib.  Every case is tiny: a few hundred contexts, pieces of at most a few hundred bytes; one
+call per algorithm and mode (test_update_long_pieces) takes pieces of 64 KiB and 1 MiB."""
 import hashlib
 
 import numpy as np
@@ -141,6 +142,42 @@ def test_update_grid(brb, torch_dev, alg, mode):
     if alg == "md5":
         assert (ctxs[:, 88:] == 0xA5).all()         # digest and string are not touched
     assert np.array_equal(after, before)            # the batch call never writes into data
+
+
+LONG_HAVES = (0, 1, 3, 60, 63)
+LONG_PIECES = (65535, 65536, 65537, (1 << 20) + 3)
+
+
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("alg", ALGS)
+def test_update_long_pieces(brb, torch_dev, alg, mode):
+    """One Update call whose pieces are far longer than a block: 64 KiB - 1, 64 KiB, 64 KiB + 1 and
+    1 MiB + 3 bytes, each onto contexts with 0, 1, 3, 60 and 63 bytes buffered, the piece addresses at
+    every residue mod 4.  The contexts equal the compat Update's byte for byte, and after Final the
+    digests equal hashlib's of the whole message."""
+    rng = np.random.default_rng(17)
+    cases = [(have, n) for n in LONG_PIECES for have in LONG_HAVES]
+    c_init, c_update, _ = compat(brb, alg)
+    heads = [rng.integers(0, 256, 64 + have, dtype=np.uint8).tobytes() for have, _ in cases]
+    ctxs = np.full((len(cases), WIDTH[alg]), 0xA5, np.uint8)
+    for r, head in enumerate(heads):
+        c_init(ctxs[r])
+        c_update(ctxs[r], head)
+    data, offs, lens = lay_out([n for _, n in cases], [r & 3 for r in range(len(cases))], rng)
+    assert {int(o) & 3 for o in offs} == {0, 1, 2, 3}
+    pieces = [data[int(o):int(o) + int(k)].tobytes() for o, k in zip(offs, lens)]
+    want = ctxs.copy()
+    for r, piece in enumerate(pieces):
+        c_update(want[r], piece)
+    before = data.copy()
+    run = Run(brb, torch_dev, alg, mode)
+    after = run.update(ctxs, data, offs, lens)
+    assert np.array_equal(after, before)            # the batch call never writes into data
+    for r, c in enumerate(cases):
+        assert have_of(alg, ctxs[r]) == (c[0] + c[1]) & 63, c
+        assert defined(alg, ctxs[r]) == defined(alg, want[r]), c
+    got = run.final(ctxs)
+    assert [got[r].tobytes() for r in range(len(cases))] == [hashed(alg, h + p) for h, p in zip(heads, pieces)]
 
 
 @pytest.mark.parametrize("alg", ALGS)
