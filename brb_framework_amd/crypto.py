@@ -157,6 +157,15 @@ _SIGNATURES = [
     ("BRB_RC4MD5_OpenBatch", ctypes.c_int,
      [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
       ctypes.c_void_p, ctypes.c_uint, ctypes.c_void_p]),
+    ("BRB_RC4_CryptListBatch", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+      ctypes.c_uint64, ctypes.c_uint, ctypes.c_void_p]),
+    ("BRB_RC4MD5_FrameListBatch", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint, ctypes.c_void_p]),
+    ("BRB_RC4MD5_OpenListBatch", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+      ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint, ctypes.c_void_p]),
     ("BRB_Base64EncodeBatch", ctypes.c_int,
      [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p,
       ctypes.c_uint, ctypes.c_void_p]),
@@ -828,6 +837,48 @@ def rc4md5_open_batch(states, frames, offsets, lengths, out=None, valid=None, st
     return out, valid
 
 
+def rc4_crypt_list_batch(states, data, buf_offsets, buf_lengths, stream_first_buf, out=None, stream=None, async_=False,
+                         all_devices=False):
+    """BRB_RC4_CryptListBatch: stream i owns buffers stream_first_buf[i] .. stream_first_buf[i + 1] - 1
+    (len(states) + 1 uint64 entries); buffer k = data[buf_offsets[k]:+buf_lengths[k]] -> out (in place when
+    out is None).  states: (n, 264) uint8, each loaded and stored once."""
+    out = data if out is None else out
+    _same_kind(data, states, out, buf_offsets, buf_lengths, stream_first_buf)
+    flags, h = _mode(data, stream, async_, all_devices)
+    _check(lib().BRB_RC4_CryptListBatch(_ptr(states), _ptr(data), _ptr(out), _ptr(buf_offsets), _ptr(buf_lengths),
+                                        _ptr(stream_first_buf), len(stream_first_buf) - 1, flags, h),
+           "BRB_RC4_CryptListBatch")
+    return out
+
+
+def rc4md5_frame_list_batch(states, payload, buf_offsets, buf_lengths, salts, frames, frame_offsets, stream_first_buf,
+                            stream=None, async_=False, all_devices=False):
+    """BRB_RC4MD5_FrameListBatch: rc4md5_frame_batch with a buffer list per stream (salts and frame_offsets
+    per buffer)."""
+    _same_kind(payload, states, buf_offsets, buf_lengths, salts, frames, frame_offsets, stream_first_buf)
+    flags, h = _mode(payload, stream, async_, all_devices)
+    _check(lib().BRB_RC4MD5_FrameListBatch(_ptr(states), _ptr(payload), _ptr(buf_offsets), _ptr(buf_lengths),
+                                           _ptr(salts), _ptr(frames), _ptr(frame_offsets), _ptr(stream_first_buf),
+                                           len(stream_first_buf) - 1, flags, h), "BRB_RC4MD5_FrameListBatch")
+    return frames
+
+
+def rc4md5_open_list_batch(states, frames, buf_offsets, buf_lengths, stream_first_buf, out=None, valid=None, stream=None,
+                           async_=False, all_devices=False):
+    """BRB_RC4MD5_OpenListBatch: rc4md5_open_batch with a buffer list per stream; returns (out, valid uint8
+    per buffer)."""
+    out = frames if out is None else out
+    nbuf = len(buf_offsets)
+    if valid is None:
+        valid = _out_like(frames, nbuf, 1).reshape(nbuf)
+    _same_kind(frames, states, out, buf_offsets, buf_lengths, stream_first_buf, valid)
+    flags, h = _mode(frames, stream, async_, all_devices)
+    _check(lib().BRB_RC4MD5_OpenListBatch(_ptr(states), _ptr(frames), _ptr(out), _ptr(buf_offsets), _ptr(buf_lengths),
+                                          _ptr(stream_first_buf), len(stream_first_buf) - 1, _ptr(valid), flags, h),
+           "BRB_RC4MD5_OpenListBatch")
+    return out, valid
+
+
 # ---- MemBuffer Blowfish (SURVEY §8 f3) ------------------------------------------------------------
 def membuf_span(data_size: int) -> int:
     """BRB_MEMBUF_SPAN: bytes a call touches after buf + offset; data_size = size + offset to
@@ -929,6 +980,7 @@ CRYPTO_FUNC_RC4, CRYPTO_FUNC_RC4_MD5 = 1, 2
 BATCHER_ZERO_COPY = 0x100
 BATCHER_PIPELINED = 0x200    # BRB_BATCHER_PIPELINED: two arenas, flush_async()
 BATCHER_ALL_DEVICES = 0x400  # BRB_BATCHER_ALL_DEVICES: connections partitioned over the devices
+BATCHER_CONN_LISTS = 0x800   # BRB_BATCHER_CONN_LISTS: one launch per direction, a buffer list per connection
 OP_READ, OP_WRITE = 0, 1
 TransformDone = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int, ctypes.c_void_p, ctypes.c_uint32,
                                  ctypes.c_int)
@@ -967,10 +1019,13 @@ class TransformBatcher:
 
     pipelined=True creates it with BRB_BATCHER_PIPELINED: flush_async() starts the round and returns
     the previous round's results; flush() drains both.  In zero-copy mode the wrapper then keeps one
-    region per arena, since a running round's buffers must stay unchanged until delivered."""
+    region per arena, since a running round's buffers must stay unchanged until delivered.
+
+    conn_lists=True creates it with BRB_BATCHER_CONN_LISTS: a round is one launch per direction, each
+    connection's buffers a list walked between one load and one store of its state."""
 
     def __init__(self, max_conns: int, max_round_bytes: int, algo: int = CRYPTO_FUNC_RC4_MD5, zero_copy: bool = False,
-                 pipelined: bool = False, all_devices: bool = False):
+                 pipelined: bool = False, all_devices: bool = False, conn_lists: bool = False):
         self._L = lib()
         n_reg = 2 if pipelined else 1
         self._regions = [HostRegion(max(max_round_bytes, 1)) for _ in range(n_reg)] if zero_copy else None
@@ -979,7 +1034,8 @@ class TransformBatcher:
         self.h = self._L.BRB_TransformBatcherCreate(max_conns, max_round_bytes,
                                                     algo | (BATCHER_ZERO_COPY if zero_copy else 0) |
                                                     (BATCHER_PIPELINED if pipelined else 0) |
-                                                    (BATCHER_ALL_DEVICES if all_devices else 0))
+                                                    (BATCHER_ALL_DEVICES if all_devices else 0) |
+                                                    (BATCHER_CONN_LISTS if conn_lists else 0))
         if not self.h:
             raise RuntimeError("BRB_TransformBatcherCreate: " + self._L.BRB_CryptoGPU_LastError().decode())
 

@@ -327,7 +327,8 @@ int BRB_CryptoGPU_TestOption(const char *name, int value, int *old)
                  {"rc4md5_pair", brb_opt::kRc4Pair, 0, 1},
                  {"rc4_pair", brb_opt::kRc4CryptPair, 0, 1},
                  {"pair_stall", brb_opt::kPairStall, 0, 1},
-                 {"bf_keyed", brb_opt::kBfKeyed, 0, 2}};
+                 {"bf_keyed", brb_opt::kBfKeyed, 0, 2},
+                 {"rc4_list_coop", brb_opt::kRc4ListCoop, 0, 1}};
     if (!name) {
         set_err("NULL option name");
         return BRB_BATCH_BADARG;

@@ -276,6 +276,42 @@ FirstList first_list(const uint64_t *first, uint64_t n, const char *name)
     return first_list(first, n, name, [](uint64_t) { return true; });
 }
 
+// The buffers a host-mode RC4 list call names: stream_first_buf checked (non-decreasing, no more buffers
+// than a launch takes), the range [k0, k0 + count) of the per-buffer arrays and the list rebased to 0.
+struct BufList {
+    bool ok = false;
+    uint64_t k0 = 0, count = 0;
+    std::vector<uint64_t> first;
+};
+
+BufList buf_list(const uint64_t *first, uint64_t n)
+{
+    BufList bl;
+    const FirstList fl = first_list(first, n, "stream_first_buf");
+    if (!fl.ok || !items_ok(fl.count))
+        return bl;
+    bl.ok = true;
+    bl.k0 = fl.k0;
+    bl.count = fl.count;
+    bl.first = fl.rebased();
+    return bl;
+}
+
+// parts_disjoint for streams that own buffer lists: stream i's written span is the span of buffers
+// first[i] .. first[i + 1] - 1 (+ extra bytes each); a stream without buffers writes nothing.
+bool stream_parts_disjoint(const uint64_t *offs, const uint32_t *lens, const uint64_t *first, uint64_t n, uint64_t extra)
+{
+    std::vector<uint64_t> so(n), sl(n);
+    for (uint64_t i = 0; i < n; i++) {
+        uint64_t lo, hi;
+        if (!span_of(offs + first[i], lens + first[i], first[i + 1] - first[i], extra, lo, hi))
+            return false;
+        so[i] = lo;
+        sl[i] = hi - lo;
+    }
+    return parts_disjoint(so.data(), sl.data(), n, 0);
+}
+
 // The contexts a host-mode call names in a context table: item i acts on ctxs[ix ? ix[i] : i].  ok() checks
 // the index list (dup_hint: what to do instead of naming a context twice); gather() is what the call stages
 // in both directions, the named contexts in item order, so the kernel runs without an index; scatter() puts
@@ -1059,6 +1095,165 @@ int BRB_RC4MD5_OpenBatch(BRB_RC4_State *states, const void *frames, void *out, c
     return st.run(s, &pf, [&] {
         return launched(brb::launch_rc4md5_open(st.dev(i_st), st.dev(i_in), st.dev(i_out), st.dev<uint64_t>(i_off),
                                                 st.dev<uint32_t>(i_len), n, st.dev(i_val), s));
+    });
+}
+
+// ---- RC4 over a buffer list per stream (rc4_list_kernels.hip) ------------------------------------
+// Stream i owns buffers first[i] .. first[i + 1] - 1 of the per-buffer arrays.  The kernels are lone
+// waves: no PairFault.  Host mode checks everything before any device work.
+
+int BRB_RC4_CryptListBatch(BRB_RC4_State *states, const void *in, void *out, const uint64_t *offsets,
+                           const uint32_t *lengths, const uint64_t *first, uint64_t n, unsigned flags, void *stream)
+{
+    t_err.clear();
+    if (n == 0)
+        return BRB_BATCH_OK;
+    if (!states || !in || !out || !offsets || !lengths || !first) {
+        set_err("NULL states, in, out, buf_offsets, buf_lengths or stream_first_buf");
+        return BRB_BATCH_BADARG;
+    }
+    if (!items_ok(n) || !flags_ok(flags))
+        return BRB_BATCH_BADARG;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (flags & BRB_BATCH_DEVICE) {
+        if (int ok = device_ok(); ok != BRB_BATCH_OK)
+            return ok;
+        return device_run(brb::launch_rc4_crypt_list(bytes(states), bytes(in), bytes(out), offsets, lengths, first, n, s), s,
+                          flags);
+    }
+    const BufList bl = buf_list(first, n);
+    if (!bl.ok)
+        return BRB_BATCH_BADARG;
+    const Span sp = span_rebase(offsets + bl.k0, lengths + bl.k0, bl.count);
+    if (!sp.ok)
+        return BRB_BATCH_BADARG;
+    if (int ok = device_ok(); ok != BRB_BATCH_OK)
+        return ok;
+    if (flags & BRB_BATCH_ALL_DEVICES) {   // streams split over the devices, states and buffer ranges with them
+        flags &= ~BRB_BATCH_ALL_DEVICES;
+        if (stream_parts_disjoint(offsets, lengths, first, n, 0))
+            return brb_host::split_devices(n, [&](int, uint64_t lo, uint64_t hi) {
+                return BRB_RC4_CryptListBatch(states + lo, in, out, offsets, lengths, first + lo, hi - lo, flags, nullptr);
+            });
+    }
+    Staging st;
+    const size_t i_st = st.inout(states, sizeof(BRB_RC4_State) * n);
+    // a separate output buffer is staged with its current bytes so that bytes outside the buffers survive
+    const size_t i_in = in == out ? st.inout(bytes(out) + sp.lo, sp.bytes()) : st.in(bytes(in) + sp.lo, sp.bytes());
+    const size_t i_out = in == out ? i_in : st.inout(bytes(out) + sp.lo, sp.bytes());
+    const size_t i_off = st.in(sp.off.data(), 8 * bl.count);
+    const size_t i_len = st.in(lengths + bl.k0, 4 * bl.count);
+    const size_t i_first = st.in(bl.first.data(), 8 * (n + 1));
+    return st.run(s, nullptr, [&] {
+        return launched(brb::launch_rc4_crypt_list(st.dev(i_st), st.dev(i_in), st.dev(i_out), st.dev<uint64_t>(i_off),
+                                                   st.dev<uint32_t>(i_len), st.dev<uint64_t>(i_first), n, s));
+    });
+}
+
+int BRB_RC4MD5_FrameListBatch(BRB_RC4_State *states, const void *payload, const uint64_t *offsets, const uint32_t *lengths,
+                              const uint64_t *salts, void *frames, const uint64_t *frame_offsets, const uint64_t *first,
+                              uint64_t n, unsigned flags, void *stream)
+{
+    t_err.clear();
+    if (n == 0)
+        return BRB_BATCH_OK;
+    if (!states || !payload || !offsets || !lengths || !salts || !frames || !frame_offsets || !first) {
+        set_err("NULL states, payload, buf_offsets, buf_lengths, salts, frames, frame_offsets or stream_first_buf");
+        return BRB_BATCH_BADARG;
+    }
+    if (!items_ok(n) || !flags_ok(flags))
+        return BRB_BATCH_BADARG;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (flags & BRB_BATCH_DEVICE) {
+        if (int ok = device_ok(); ok != BRB_BATCH_OK)
+            return ok;
+        return device_run(brb::launch_rc4md5_frame_list(bytes(states), bytes(payload), offsets, lengths, salts, bytes(frames),
+                                                        frame_offsets, first, n, s),
+                          s, flags);
+    }
+    const BufList bl = buf_list(first, n);
+    if (!bl.ok)
+        return BRB_BATCH_BADARG;
+    const Span sp = span_rebase(offsets + bl.k0, lengths + bl.k0, bl.count);
+    if (!sp.ok)
+        return BRB_BATCH_BADARG;
+    const Span sf = span_rebase(frame_offsets + bl.k0, lengths + bl.k0, bl.count, BRB_RC4MD5_HEADER);
+    if (!sf.ok)
+        return BRB_BATCH_BADARG;
+    if (int ok = device_ok(); ok != BRB_BATCH_OK)
+        return ok;
+    if (flags & BRB_BATCH_ALL_DEVICES) {   // frames are written back: the parts' frame spans must not interleave
+        flags &= ~BRB_BATCH_ALL_DEVICES;
+        if (stream_parts_disjoint(frame_offsets, lengths, first, n, BRB_RC4MD5_HEADER))
+            return brb_host::split_devices(n, [&](int, uint64_t lo, uint64_t hi) {
+                return BRB_RC4MD5_FrameListBatch(states + lo, payload, offsets, lengths, salts, frames, frame_offsets,
+                                                 first + lo, hi - lo, flags, nullptr);
+            });
+    }
+    Staging st;
+    const size_t i_st = st.inout(states, sizeof(BRB_RC4_State) * n);
+    const size_t i_pl = st.in(bytes(payload) + sp.lo, sp.bytes());
+    const size_t i_fr = st.inout(bytes(frames) + sf.lo, sf.bytes());
+    const size_t i_po = st.in(sp.off.data(), 8 * bl.count);
+    const size_t i_fo = st.in(sf.off.data(), 8 * bl.count);
+    const size_t i_len = st.in(lengths + bl.k0, 4 * bl.count);
+    const size_t i_salt = st.in(salts + bl.k0, 8 * bl.count);
+    const size_t i_first = st.in(bl.first.data(), 8 * (n + 1));
+    return st.run(s, nullptr, [&] {
+        return launched(brb::launch_rc4md5_frame_list(st.dev(i_st), st.dev(i_pl), st.dev<uint64_t>(i_po),
+                                                      st.dev<uint32_t>(i_len), st.dev<uint64_t>(i_salt), st.dev(i_fr),
+                                                      st.dev<uint64_t>(i_fo), st.dev<uint64_t>(i_first), n, s));
+    });
+}
+
+int BRB_RC4MD5_OpenListBatch(BRB_RC4_State *states, const void *frames, void *out, const uint64_t *offsets,
+                             const uint32_t *lengths, const uint64_t *first, uint64_t n, uint8_t *valid, unsigned flags,
+                             void *stream)
+{
+    t_err.clear();
+    if (n == 0)
+        return BRB_BATCH_OK;
+    if (!states || !frames || !out || !offsets || !lengths || !first || !valid) {
+        set_err("NULL states, frames, out, buf_offsets, buf_lengths, stream_first_buf or valid");
+        return BRB_BATCH_BADARG;
+    }
+    if (!items_ok(n) || !flags_ok(flags))
+        return BRB_BATCH_BADARG;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (flags & BRB_BATCH_DEVICE) {
+        if (int ok = device_ok(); ok != BRB_BATCH_OK)
+            return ok;
+        return device_run(brb::launch_rc4md5_open_list(bytes(states), bytes(frames), bytes(out), offsets, lengths, first, n,
+                                                       valid, s),
+                          s, flags);
+    }
+    const BufList bl = buf_list(first, n);
+    if (!bl.ok)
+        return BRB_BATCH_BADARG;
+    const Span sp = span_rebase(offsets + bl.k0, lengths + bl.k0, bl.count);
+    if (!sp.ok)
+        return BRB_BATCH_BADARG;
+    if (int ok = device_ok(); ok != BRB_BATCH_OK)
+        return ok;
+    if (flags & BRB_BATCH_ALL_DEVICES) {
+        flags &= ~BRB_BATCH_ALL_DEVICES;
+        if (stream_parts_disjoint(offsets, lengths, first, n, 0))
+            return brb_host::split_devices(n, [&](int, uint64_t lo, uint64_t hi) {
+                return BRB_RC4MD5_OpenListBatch(states + lo, frames, out, offsets, lengths, first + lo, hi - lo, valid, flags,
+                                                nullptr);
+            });
+    }
+    Staging st;
+    const size_t i_st = st.inout(states, sizeof(BRB_RC4_State) * n);
+    const size_t i_in = frames == out ? st.inout(bytes(out) + sp.lo, sp.bytes()) : st.in(bytes(frames) + sp.lo, sp.bytes());
+    const size_t i_out = frames == out ? i_in : st.inout(bytes(out) + sp.lo, sp.bytes());
+    const size_t i_off = st.in(sp.off.data(), 8 * bl.count);
+    const size_t i_len = st.in(lengths + bl.k0, 4 * bl.count);
+    const size_t i_first = st.in(bl.first.data(), 8 * (n + 1));
+    const size_t i_val = st.out(valid + bl.k0, bl.count);
+    return st.run(s, nullptr, [&] {
+        return launched(brb::launch_rc4md5_open_list(st.dev(i_st), st.dev(i_in), st.dev(i_out), st.dev<uint64_t>(i_off),
+                                                     st.dev<uint32_t>(i_len), st.dev<uint64_t>(i_first), n, st.dev(i_val), s));
     });
 }
 

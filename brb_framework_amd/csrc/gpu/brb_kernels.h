@@ -93,6 +93,20 @@ hipError_t launch_rc4md5_open(uint8_t *states, const uint8_t *in, uint8_t *out, 
                               const uint32_t *lens, uint64_t n, uint8_t *valid, hipStream_t s,
                               const uint32_t *sidx = nullptr, const uint64_t *ooffs = nullptr);
 
+// RC4 over a buffer list per stream (rc4_list_kernels.hip): stream i loads states[sidx ? sidx[i] : i]
+// once, walks buffers first[i] .. first[i + 1] - 1 (first: n + 1 non-decreasing entries) in order, each
+// exactly as the launcher above treats its one buffer, and stores the state once.  offs, lens, ooffs,
+// salts, foffs and valid are indexed by buffer.  Lone-wave kernels: no pair fault word is involved.
+hipError_t launch_rc4_crypt_list(uint8_t *states, const uint8_t *in, uint8_t *out, const uint64_t *offs,
+                                 const uint32_t *lens, const uint64_t *first, uint64_t n, hipStream_t s,
+                                 const uint32_t *sidx = nullptr, const uint64_t *ooffs = nullptr);
+hipError_t launch_rc4md5_frame_list(uint8_t *states, const uint8_t *payload, const uint64_t *offs, const uint32_t *lens,
+                                    const uint64_t *salts, uint8_t *frames, const uint64_t *foffs,
+                                    const uint64_t *first, uint64_t n, hipStream_t s, const uint32_t *sidx = nullptr);
+hipError_t launch_rc4md5_open_list(uint8_t *states, const uint8_t *in, uint8_t *out, const uint64_t *offs,
+                                   const uint32_t *lens, const uint64_t *first, uint64_t n, uint8_t *valid,
+                                   hipStream_t s, const uint32_t *sidx = nullptr, const uint64_t *ooffs = nullptr);
+
 // Key setup (keysetup_kernels.hip): key i = keys[koffs[i] .. + klens[i]).
 // RC4: the zeroed-then-BRB_RC4_Init state of key i is written (all 264 bytes) to states[slots ? slots[i] : i],
 // and, when second != 0, also `second` bytes after it (the transform batcher's write-state table).

@@ -30,10 +30,12 @@ enum Opt {
                         // tests see a bounded wait give up and the call report it (pair_fault.h); 0: off
     kBfKeyed = 14,      // keyed Blowfish ECB (blowfish_keyed_kernels.hip): 0 spread fill, 2 blocks per lane (default);
                         // 1 the plain fill; 2 one block per lane.  The MemBuffer decrypt stop always runs the default
-    kCount = 15
+    kRc4ListCoop = 15,  // RC4 pass over buffer lists (rc4_list_kernels.hip): 1 cooperative block loads, buffer ranks
+                        // walked wave-uniformly (default); 0 per-lane block loads
+    kCount = 16
 };
 
-inline std::atomic<int> g_opt[kCount] = {-1, 1, 1, 1, 0, -1, 0, 0, 2, 2, 0, 1, 1, 0, 0};
+inline std::atomic<int> g_opt[kCount] = {-1, 1, 1, 1, 0, -1, 0, 0, 2, 2, 0, 1, 1, 0, 0, 1};
 
 inline int get(Opt o) { return g_opt[o].load(std::memory_order_relaxed); }
 

@@ -11,6 +11,10 @@
 // Ordering: a connection's buffers in one direction form one RC4 stream, so a round may hold at
 // most one of them per sub-round; the k-th buffer of a connection in a round runs in sub-round k.
 //
+// Connection lists (BRB_BATCHER_CONN_LISTS): every (direction, connection) of a round is one stream of
+// the list kernels (rc4_list_kernels.hip), its buffers in submission order, so the round is one
+// launch per direction -- READ, then WRITE -- and a state is loaded and stored once per round.
+//
 // Zero-copy rounds (BRB_BATCHER_ZERO_COPY): the callers' buffers are page-locked, Read/Write keep a
 // reference instead of copying them into the arena, the kernels read them over PCIe and write the
 // results straight into the page-locked output arena.  The copy mode spent ~60 % of a round in the
@@ -37,7 +41,11 @@ namespace {
 
 constexpr uint32_t kHdr = BRB_RC4MD5_HEADER;
 constexpr size_t kAlign = 256;    // arenas
-constexpr size_t kMetaItem = 80;  // metadata bytes budgeted per buffer: 32 of arrays + up to 40 of padding + valid
+// metadata bytes budgeted per buffer: 32 of arrays + up to 40 of padding + valid.  Connection lists
+// (BRB_BATCHER_CONN_LISTS): 28 of per-buffer arrays + 12 per stream (sidx and `first`; a group has no
+// more streams than buffers) + valid = 41; the 8 bytes of each group's extra `first` entry and the
+// padding of its six arrays (two groups) come out of meta_cap's fixed 4096.
+constexpr size_t kMetaItem = 80;
 
 inline size_t up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
@@ -51,6 +59,7 @@ struct Item {
     uint64_t salt;
     uint32_t round;   // sub-round
     uint32_t epoch;   // the connection's key epoch at submission (BRB_TransformBatcher::epoch)
+    uint32_t pos;     // connection lists: the buffer's index in its direction's group (list order)
 };
 
 // Page-locked host ranges registered through BRB_CryptoGPU_HostRegister: host base, length, the
@@ -214,6 +223,7 @@ struct BRB_TransformBatcher {
     uint64_t cap = 0;          // input bytes per round
     int algo = 0;
     bool zc = false;           // zero-copy rounds
+    bool lists = false;        // BRB_BATCHER_CONN_LISTS: one launch per direction, a buffer list per connection
     int n_rounds = 1;          // 2 when pipelined
     int cur = 0;               // the round Read/Write fill
     int dev = 0;
@@ -335,7 +345,8 @@ BRB_TransformBatcher *BRB_TransformBatcherCreate(uint32_t max_conns, uint64_t ma
     }
     const bool zc = (algo & BRB_BATCHER_ZERO_COPY) != 0;
     const bool pipelined = (algo & BRB_BATCHER_PIPELINED) != 0;
-    algo &= ~(BRB_BATCHER_ZERO_COPY | BRB_BATCHER_PIPELINED);
+    const bool lists = (algo & BRB_BATCHER_CONN_LISTS) != 0;
+    algo &= ~(BRB_BATCHER_ZERO_COPY | BRB_BATCHER_PIPELINED | BRB_BATCHER_CONN_LISTS);
     if (max_conns == 0 || max_round_bytes == 0 || (algo != BRB_CRYPTO_FUNC_RC4 && algo != BRB_CRYPTO_FUNC_RC4_MD5)) {
         set_err("max_conns and max_round_bytes must be > 0 and algo RC4 (1) or RC4_MD5 (2)");
         return nullptr;
@@ -351,6 +362,7 @@ BRB_TransformBatcher *BRB_TransformBatcherCreate(uint32_t max_conns, uint64_t ma
     b->cap = max_round_bytes;
     b->algo = algo;
     b->zc = zc;
+    b->lists = lists;
     b->n_rounds = pipelined ? 2 : 1;
     b->enabled.assign(max_conns, 0);
     b->epoch.assign(max_conns, 0);
@@ -691,15 +703,78 @@ static int enqueue_round(BRB_TransformBatcher *b, Round &R, bool *started)
         rounds = std::max(rounds, it.round + 1);
     }
     // metadata: per (sub-round, op) a contiguous group: sidx u32[], offs u64[], lens u32[], ooffs u64[], salts u64[]
+    // connection lists: per op one group: sidx u32[streams], first u64[streams + 1], then the per-buffer arrays
     struct Group {
         int op;
-        uint32_t count;
+        uint32_t count;     // buffers
         size_t o_sidx, o_offs, o_lens, o_ooffs, o_salts;
+        uint32_t streams;   // connection lists: (direction, connection) streams of the group
+        size_t o_first;
     };
     std::vector<Group> groups;
-    R.group_of.assign(size_t(rounds) * 2, -1);
+    R.group_of.assign(b->lists ? 2 : size_t(rounds) * 2, -1);
     size_t m = 0;
-    for (uint32_t r = 0; r < rounds; r++)
+    for (int op = 0; b->lists && op < 2; op++) {   // READ first, then WRITE
+        // streams in order of first appearance, a stream's buffers in submission order
+        uint32_t *sid = seen.data() + size_t(op) * b->max_conns;   // connection -> stream + 1
+        std::fill(sid, sid + b->max_conns, 0u);
+        std::vector<uint32_t> conns;
+        std::vector<uint64_t> next;        // stream -> its buffer count, then the next free buffer index
+        uint32_t c = 0;
+        for (const Item &it : R.items) {
+            if (it.op != op)
+                continue;
+            if (!sid[it.conn]) {
+                conns.push_back(it.conn);
+                next.push_back(0);
+                sid[it.conn] = uint32_t(conns.size());
+            }
+            ++next[sid[it.conn] - 1];
+            ++c;
+        }
+        if (!c)
+            continue;
+        const size_t ns = conns.size();
+        Group g{op, c, 0, 0, 0, 0, 0, uint32_t(ns), 0};
+        g.o_sidx = m;
+        m = up(m + 4 * ns, 8);
+        g.o_first = m;
+        m = up(m + 8 * (ns + 1), 8);
+        g.o_offs = m;
+        m = up(m + 8 * size_t(c), 8);
+        g.o_lens = m;
+        m = up(m + 4 * size_t(c), 8);
+        g.o_ooffs = m;
+        m = up(m + 8 * size_t(c), 8);
+        g.o_salts = m;
+        m = up(m + 8 * size_t(c), 8);
+        if (m > b->meta_cap) {
+            set_err("metadata overflow");
+            return BRB_BATCH_NOT_DONE;
+        }
+        uint64_t *first = reinterpret_cast<uint64_t *>(R.h_meta + g.o_first);
+        uint64_t at = 0;
+        for (size_t i = 0; i < ns; i++) {
+            reinterpret_cast<uint32_t *>(R.h_meta + g.o_sidx)[i] = uint32_t(op) * b->max_conns + conns[i];
+            first[i] = at;
+            at += next[i];
+            next[i] = first[i];
+        }
+        first[ns] = at;
+        for (Item &it : R.items) {
+            if (it.op != op)
+                continue;
+            const uint64_t k = next[sid[it.conn] - 1]++;
+            it.pos = uint32_t(k);
+            reinterpret_cast<uint64_t *>(R.h_meta + g.o_offs)[k] = b->zc ? it.in_off - uint64_t(R.out_dev) : it.in_off;
+            reinterpret_cast<uint32_t *>(R.h_meta + g.o_lens)[k] = it.in_len;
+            reinterpret_cast<uint64_t *>(R.h_meta + g.o_ooffs)[k] = it.out_off;
+            reinterpret_cast<uint64_t *>(R.h_meta + g.o_salts)[k] = it.salt;
+        }
+        R.group_of[op] = int64_t(groups.size());
+        groups.push_back(g);
+    }
+    for (uint32_t r = 0; !b->lists && r < rounds; r++)
         for (int op = 0; op < 2; op++) {
             uint32_t c = 0;
             for (const Item &it : R.items)
@@ -773,7 +848,26 @@ static int enqueue_round(BRB_TransformBatcher *b, Round &R, bool *started)
         const uint64_t *salts = reinterpret_cast<const uint64_t *>(R.d_meta + g.o_salts);
         if (int64_t(gi) == b->fault_launch)
             return fail_hip("kernel launch (injected fault)", hipErrorLaunchFailure);
-        if (b->zc) {
+        if (b->lists) {
+            // the launches below with a buffer list per connection (rc4_list_kernels.hip)
+            const uint64_t *first = reinterpret_cast<const uint64_t *>(R.d_meta + g.o_first);
+            if (b->algo == BRB_CRYPTO_FUNC_RC4) {
+                e = b->zc ? brb::launch_rc4_crypt_list(b->d_states, zbase, zbase, offs, lens, first, g.streams, s, sidx, ooffs)
+                          : brb::launch_rc4_crypt_list(b->d_states, R.d_in, R.d_out, offs, lens, first, g.streams, s, sidx);
+            } else if (g.op == BRB_CRYPTO_OP_WRITE) {
+                e = b->zc ? brb::launch_rc4md5_frame_list(b->d_states, zbase, offs, lens, salts, zbase, ooffs, first,
+                                                          g.streams, s, sidx)
+                          : brb::launch_rc4md5_frame_list(b->d_states, R.d_in, offs, lens, salts, R.d_out, ooffs, first,
+                                                          g.streams, s, sidx);
+            } else {
+                R.group_valid[gi] = vpos;
+                e = b->zc ? brb::launch_rc4md5_open_list(b->d_states, zbase, zbase, offs, lens, first, g.streams,
+                                                         zvalid + vpos, s, sidx, ooffs)
+                          : brb::launch_rc4md5_open_list(b->d_states, R.d_in, R.d_in, offs, lens, first, g.streams,
+                                                         R.d_meta + vpos, s, sidx);
+                vpos += g.count;
+            }
+        } else if (b->zc) {
             // inputs read in place over PCIe, outputs written into the page-locked output arena
             if (b->algo == BRB_CRYPTO_FUNC_RC4) {
                 e = brb::launch_rc4_crypt(b->d_states, zbase, zbase, offs, lens, g.count, s, sidx, ooffs, true);
@@ -876,8 +970,9 @@ static int64_t deliver_round(BRB_TransformBatcher *b, Round &R, BRB_TransformDon
     std::vector<uint32_t> next_in_group(R.group_valid.size(), 0);
     int64_t delivered = 0;
     for (const Item &it : R.items) {
-        const int64_t gi = R.group_of[size_t(it.round) * 2 + it.op];
-        const uint32_t k = next_in_group[gi]++;
+        // connection lists: one group per direction, valid flags in list order (Item::pos)
+        const int64_t gi = R.group_of[b->lists ? size_t(it.op) : size_t(it.round) * 2 + it.op];
+        const uint32_t k = b->lists ? it.pos : next_in_group[gi]++;
         if (poisoned(b, it)) {          // ran on states a faulted round before it left out of step
             ++*n_stale;
             if (done)

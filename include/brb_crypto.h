@@ -459,6 +459,51 @@ int BRB_RC4MD5_OpenBatch(BRB_RC4_State *states, const void *frames, void *out, c
                          const uint32_t *lengths, uint64_t n, uint8_t *valid, unsigned flags,
                          void *hip_stream);
 
+/* ---- The three calls above with a buffer list per stream --------------------------------------
+ * A connection that queued several buffers in one event-loop round (one aio_req per
+ * EvAIOReqTransform_WriteData) needs one call per buffer above, each loading and storing its state.
+ * Here stream i owns buffers stream_first_buf[i] .. stream_first_buf[i + 1] - 1 (n_streams + 1
+ * entries, non-decreasing, as rec_first_seg of BRB_MD5BatchSegments); buf_offsets, buf_lengths,
+ * salts, frame_offsets and valid are indexed by buffer.  One launch: states[i] is read once, the
+ * stream's buffers are processed in list order, states[i] is written once.  The result -- outputs,
+ * valid flags and all 264 bytes of every state -- is exactly what the scalar calls leave when applied
+ * to the stream's buffers in list order with states[i]: BRB_RC4_Crypt per buffer (CryptList); the
+ * WRITE side of EvAIOReqTransform_CryptoRaw(RC4_MD5) per buffer (FrameList); the READ side plus
+ * EvAIOReqTransform_RC4_MD5_DataValidate per buffer (OpenList: a frame shorter than 30 bytes is
+ * decrypted and reported invalid, a failed check changes nothing else, and the stream goes on with
+ * its next buffer).  With one buffer per stream the outputs and states are those of the calls above.
+ * A stream without buffers keeps its state bit for bit; an empty buffer reads and writes nothing and
+ * its offset need not be memory.  out may equal in / frames.  Buffers of one call must not overlap
+ * each other; frames must not overlap each other or any payload of the call; bytes between buffers
+ * keep their values.
+ * Flags, return codes and hip_stream as BRB_RC4_CryptBatch.  BRB_BATCH_DEVICE (optionally
+ * BRB_BATCH_ASYNC): every pointer is device memory, states are 4-byte aligned, nothing is allocated
+ * (graph-capturable) and nothing is validated beyond NULL pointers, the stream count and the flags.
+ * BRB_BATCH_HOST returns -1 with a reason, and writes nothing, for: a NULL required pointer; a
+ * stream_first_buf that decreases; an offset + length (+ 30 for frames) that wraps; more streams or
+ * buffers than a launch takes; BRB_BATCH_ALL_DEVICES with BRB_BATCH_DEVICE.  Host mode stages the
+ * n_streams states in both directions, the span of the named buffers (outputs in both directions, so
+ * bytes between buffers survive), the index arrays, and valid out.  BRB_BATCH_ALL_DEVICES (host mode)
+ * splits the streams into contiguous ranges, their buffer ranges with them, only when the parts'
+ * written byte spans do not interleave (as BRB_RC4_CryptBatch); otherwise the call runs on the
+ * calling thread's device.  n_streams == 0 returns 1 and touches nothing.  One wave per 64 streams, no
+ * wave pairs: BRB_BATCH_FAULT never occurs.  No CPU fallback: without a usable device the call
+ * returns 0 with the reason in BRB_CryptoGPU_LastError(). */
+int BRB_RC4_CryptListBatch(BRB_RC4_State *states, const void *in, void *out, const uint64_t *buf_offsets,
+                           const uint32_t *buf_lengths, const uint64_t *stream_first_buf, uint64_t n_streams,
+                           unsigned flags, void *hip_stream);
+/* Buffer k: frames[frame_offsets[k] .. + 30 + buf_lengths[k]) = the frame of payload[buf_offsets[k] ..
+ * + buf_lengths[k]) with salts[k], encrypted with its stream's state (BRB_RC4MD5_FrameBatch). */
+int BRB_RC4MD5_FrameListBatch(BRB_RC4_State *states, const void *payload, const uint64_t *buf_offsets,
+                              const uint32_t *buf_lengths, const uint64_t *salts, void *frames,
+                              const uint64_t *frame_offsets, const uint64_t *stream_first_buf, uint64_t n_streams,
+                              unsigned flags, void *hip_stream);
+/* Buffer k: frame k = frames[buf_offsets[k] .. + buf_lengths[k]) is decrypted into out at the same
+ * offset and valid[k] is set (BRB_RC4MD5_OpenBatch). */
+int BRB_RC4MD5_OpenListBatch(BRB_RC4_State *states, const void *frames, void *out, const uint64_t *buf_offsets,
+                             const uint32_t *buf_lengths, const uint64_t *stream_first_buf, uint64_t n_streams,
+                             uint8_t *valid, unsigned flags, void *hip_stream);
+
 /* ---- Receive-loop batching ------------------------------------------------------
  * The comm layer calls the transform hook once per buffer on the thread that owns the connection
  * (EvAIOReqTransform_ReadData / _WriteData, ev_kq_aio_transform.c:42-70, from comm_tcp_server.c:1749,
@@ -494,6 +539,14 @@ int BRB_RC4MD5_OpenBatch(BRB_RC4_State *states, const void *frames, void *out, c
  * connections on different devices are not interleaved in submission order.  With one device (or
  * max_conns < G) this is a plain batcher. */
 #define BRB_BATCHER_ALL_DEVICES   0x400
+/* OR into `algo` at Create: connection lists.  A round runs as one launch per direction (the READ
+ * group, then the WRITE group) whatever the number of buffers per connection: each (direction,
+ * connection) is one stream of the list calls above, its buffers in submission order, so a
+ * connection's state is loaded and stored once per round and direction instead of once per buffer.
+ * Results, callback order, GetState, key epochs and the dropped-round and poisoning rules are those of
+ * a batcher without the flag; it combines with the three flags above (an all-devices batcher passes it
+ * to its parts).  The list kernels run one wave per 64 connections, not wave pairs. */
+#define BRB_BATCHER_CONN_LISTS    0x800
 typedef struct BRB_TransformBatcher BRB_TransformBatcher;
 typedef void (*BRB_TransformDone)(void *user, uint32_t conn, int op, const void *out, uint32_t out_len, int valid);
 /* `valid` of a buffer whose round was dropped (out = NULL, out_len = 0): see Flush. */
@@ -557,7 +610,8 @@ int64_t BRB_TransformBatcherFlushAsync(BRB_TransformBatcher *b, BRB_TransformDon
 int BRB_TransformBatcherGetState(BRB_TransformBatcher *b, uint32_t conn, int op, BRB_RC4_State *out);
 /* Test support, not for production use: from now on the `launch`-th kernel launch (0-based) of every
  * round reports a failure without running, so a test can watch a round being dropped; -1 turns it
- * off.  Returns 1, or -1 for a NULL batcher.  (Replaces round 2's BRB_TEST_BATCHER_FAULT variable:
+ * off.  A round launches one kernel per direction and sub-round (READ before WRITE in each sub-round);
+ * with BRB_BATCHER_CONN_LISTS one per direction, so at most two.  Returns 1, or -1 for a NULL batcher.  (Replaces round 2's BRB_TEST_BATCHER_FAULT variable:
  * the library reads no environment variable.) */
 int BRB_TransformBatcherInjectFault(BRB_TransformBatcher *b, int launch);
 
@@ -669,7 +723,8 @@ int BRB_CryptoGPU_HostUnregister(void *p);
  * pass and RC4+MD5 frame / open wave pairs get a protocol fault injected, so the call returns
  * BRB_BATCH_FAULT, an async call's check reports it and a batcher round is dropped), "bf_keyed" 0/1/2
  * (the keyed Blowfish ECB calls: spread image fill and two blocks per lane / the plain fill / one
- * block per lane).  Returns 1 and the previous
+ * block per lane), "rc4_list_coop" 1/0 (BRB_RC4_CryptListBatch: cooperative / per-lane block
+ * loads).  Returns 1 and the previous
  * value in *old (if not NULL), or -1 for an unknown name or a value out of range. */
 int BRB_CryptoGPU_TestOption(const char *name, int value, int *old);
 /* Test support, not for production use: the kernel that BRB_MD5BatchFixed / BrbSha1_BatchFixed run
