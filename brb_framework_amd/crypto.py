@@ -124,6 +124,13 @@ _SIGNATURES = [
     ("BrbSha1_UpdateSegmentsBatch", ctypes.c_int,
      [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
       ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint, ctypes.c_void_p]),
+    ("BRB_MD5LowerTextBatch", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p,
+      ctypes.c_uint, ctypes.c_void_p]),
+    ("BRB_MD5UpdateSegmentsLowerBatch", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint,
+      ctypes.c_void_p]),
     ("BRB_Blowfish_EncryptBatch", ctypes.c_int,
      [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint, ctypes.c_void_p]),
     ("BRB_Blowfish_DecryptBatch", ctypes.c_int,
@@ -379,6 +386,29 @@ def md5_batch(data, offsets, lengths, out=None, stream=None, async_=False, all_d
     return _digest_var(lib().BRB_MD5Batch, 16, data, offsets, lengths, out, stream, async_, all_devices)
 
 
+def md5_lower_text_batch(data, offsets, lengths, out=None, strings=None, want_strings=False, stream=None, async_=False,
+                          all_devices=False):
+    """BRB_MD5LowerTextBatch: the MD5 of key i = data[offsets[i]:+lengths[i]] lower-cased as BRB_MD5UpdateLowerText
+    does ('A'..'Z' only), without a context.  Returns the digests (n, 16); with `strings` given or want_strings,
+    (digests, strings), strings (n, 33) uint8 holding 32 lower-case hex characters and a NUL per key."""
+    _same_kind(data, offsets, lengths, out, strings)
+    n = len(offsets)
+    if len(lengths) != n:
+        raise ValueError("offsets and lengths differ in length")
+    if out is None:
+        out = _out_like(data, n, 16)
+    elif _nbytes(out) < n * 16:
+        raise ValueError(f"out holds {_nbytes(out)} bytes, {n} digests need {n * 16}")
+    if strings is None and want_strings:
+        strings = _out_like(data, n, 33)
+    elif strings is not None and _nbytes(strings) < n * 33:
+        raise ValueError(f"strings holds {_nbytes(strings)} bytes, {n} keys need {n * 33}")
+    flags, h = _mode(data, stream, async_, all_devices)
+    _check(lib().BRB_MD5LowerTextBatch(_ptr(data), _ptr(offsets), _ptr(lengths), n, _ptr(out), _ptr(strings), flags, h),
+           "BRB_MD5LowerTextBatch")
+    return out if strings is None else (out, strings)
+
+
 def md5_batch_segments(data, seg_offsets, seg_lengths, rec_first_seg, out=None, stream=None, async_=False,
                        all_devices=False):
     """BRB_MD5BatchSegments: record i = concatenation of segments rec_first_seg[i] .. rec_first_seg[i+1]-1
@@ -495,6 +525,13 @@ def md5_ctx_update(row, piece) -> None:
     lib().BRB_MD5Update(_ctx_row(row, BRB_MD5_CTX), ctypes.create_string_buffer(piece, max(len(piece), 1)), len(piece))
 
 
+def md5_ctx_update_lower(row, piece) -> None:
+    """BRB_MD5UpdateLowerText (host, compat) of one row with `piece` (bytes): 'A'..'Z' lower-cased on the way in."""
+    piece = bytes(piece)
+    lib().BRB_MD5UpdateLowerText(_ctx_row(row, BRB_MD5_CTX), ctypes.create_string_buffer(piece, max(len(piece), 1)),
+                                 len(piece))
+
+
 def md5_ctx_final(row) -> bytes:
     """BRB_MD5Final (host, compat) of one row; returns the 16 digest bytes."""
     lib().BRB_MD5Final(_ctx_row(row, BRB_MD5_CTX))
@@ -562,8 +599,15 @@ def _stream_final(fn, width, dig, ctxs, ctx_index, n, out, stream, async_, all_d
 
 
 def _stream_segments(fn, width, dig, ctxs, data, seg_offsets, seg_lengths, item_first_seg, final, ctx_index, out, stream,
-                     async_, all_devices):
-    _same_kind(ctxs, data, seg_offsets, seg_lengths, item_first_seg, final, ctx_index, out)
+                     async_, all_devices, seg_lower=False):
+    """seg_lower: False for the calls without the list; else BRB_MD5UpdateSegmentsLowerBatch's (None: NULL)."""
+    if seg_lower is False:
+        seg_lower, lower = None, ()
+    else:
+        lower = (_ptr(seg_lower),)
+    if seg_lower is not None and (len(seg_lower) != len(seg_lengths) or _nbytes(seg_lower) != len(seg_lengths)):
+        raise ValueError("seg_lower is one byte per segment")
+    _same_kind(ctxs, data, seg_offsets, seg_lengths, item_first_seg, final, ctx_index, out, seg_lower)
     n_ctx, n = _stream_n(ctxs, width, ctx_index, len(item_first_seg) - 1)
     if n < 0 or len(seg_offsets) != len(seg_lengths):
         raise ValueError("item_first_seg needs n + 1 entries, and seg_offsets as many as seg_lengths")
@@ -578,8 +622,8 @@ def _stream_segments(fn, width, dig, ctxs, data, seg_offsets, seg_lengths, item_
         elif _nbytes(out) < n * dig:
             raise ValueError(f"out holds {_nbytes(out)} bytes, {n} digests need {n * dig}")
     flags, h = _mode(ctxs, stream, async_, all_devices)
-    _check(fn(_ptr(ctxs), n_ctx, _ptr(ctx_index), _ptr(data), _ptr(seg_offsets), _ptr(seg_lengths), _ptr(item_first_seg),
-              n, _ptr(final), _ptr(out), flags, h), fn.__name__)
+    _check(fn(_ptr(ctxs), n_ctx, _ptr(ctx_index), _ptr(data), _ptr(seg_offsets), _ptr(seg_lengths), *lower,
+              _ptr(item_first_seg), n, _ptr(final), _ptr(out), flags, h), fn.__name__)
     return out
 
 
@@ -592,6 +636,14 @@ def md5_update_segments_batch(ctxs, data, seg_offsets, seg_lengths, item_first_s
     None when final is None."""
     return _stream_segments(lib().BRB_MD5UpdateSegmentsBatch, MD5_CTX_BYTES, 16, ctxs, data, seg_offsets, seg_lengths,
                             item_first_seg, final, ctx_index, out, stream, async_, all_devices)
+
+
+def md5_update_segments_lower_batch(ctxs, data, seg_offsets, seg_lengths, item_first_seg, seg_lower=None, final=None,
+                                    ctx_index=None, out=None, stream=None, async_=False, all_devices=False):
+    """BRB_MD5UpdateSegmentsLowerBatch: md5_update_segments_batch with seg_lower, uint8 per segment -- != 0 takes the
+    segment as BRB_MD5UpdateLowerText, 0 as BRB_MD5UpdateBig; None: every segment is lower-cased."""
+    return _stream_segments(lib().BRB_MD5UpdateSegmentsLowerBatch, MD5_CTX_BYTES, 16, ctxs, data, seg_offsets, seg_lengths,
+                            item_first_seg, final, ctx_index, out, stream, async_, all_devices, seg_lower=seg_lower)
 
 
 def sha1_update_segments_batch(ctxs, data, seg_offsets, seg_lengths, item_first_seg, final=None, ctx_index=None, out=None,

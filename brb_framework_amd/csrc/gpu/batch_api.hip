@@ -487,10 +487,13 @@ int digest_stream(bool sha1, StreamOp op, void *ctxs, uint64_t n_ctx, const uint
 // BRB_MD5UpdateSegmentsBatch / BrbSha1_UpdateSegmentsBatch: item i advances ctxs[ctx_index ? ctx_index[i] : i] by
 // the segments first[i] .. first[i + 1] - 1 and is then finalised when fin && fin[i].  digest_stream's index checks
 // and context staging, BRB_MD5BatchSegments' segment staging; the digests are staged in both directions, so the rows
-// of items that are not finalised keep the caller's bytes.
+// of items that are not finalised keep the caller's bytes.  lower (BRB_MD5UpdateSegmentsLowerBatch, MD5 only): segment
+// k is taken as BRB_MD5UpdateLowerText when slow[k] != 0, every segment when slow is NULL; slow is staged over the
+// named segment range like the lengths.
 int digest_stream_segments(bool sha1, void *ctxs, uint64_t n_ctx, const uint32_t *ctx_index, const void *data,
                            const uint64_t *soff, const uint32_t *slen, const uint64_t *first, uint64_t n,
-                           const uint8_t *fin, void *digests, unsigned flags, void *stream)
+                           const uint8_t *fin, void *digests, unsigned flags, void *stream, bool lower = false,
+                           const uint8_t *slow = nullptr)
 {
     t_err.clear();
     if (n == 0)
@@ -505,12 +508,15 @@ int digest_stream_segments(bool sha1, void *ctxs, uint64_t n_ctx, const uint32_t
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (!fin)
         digests = nullptr;                           // no item is finalised: not used
+    auto launch = [&](uint8_t *c, const uint32_t *ix, const uint8_t *d, const uint64_t *o, const uint32_t *l, const uint8_t *w,
+                      const uint64_t *f, const uint8_t *fi, uint8_t *dg) {
+        return lower ? brb::launch_md5_stream_segments_lower(c, ix, d, o, l, w, f, n, fi, dg, s)
+                     : brb::launch_digest_stream_segments(sha1, c, ix, d, o, l, f, n, fi, dg, s);
+    };
     if (flags & BRB_BATCH_DEVICE) {
         if (int ok = device_ok(); ok != BRB_BATCH_OK)
             return ok;
-        return device_run(brb::launch_digest_stream_segments(sha1, bytes(ctxs), ctx_index, bytes(data), soff, slen, first, n,
-                                                             fin, bytes(digests), s),
-                          s, flags);
+        return device_run(launch(bytes(ctxs), ctx_index, bytes(data), soff, slen, slow, first, fin, bytes(digests)), s, flags);
     }
     // host mode: every list is host memory and is checked before anything runs
     NamedCtx named{bytes(ctxs), ctx_index, n, stride, {}};
@@ -534,7 +540,7 @@ int digest_stream_segments(bool sha1, void *ctxs, uint64_t n_ctx, const uint32_t
             return digest_stream_segments(sha1, ctx_index ? ctxs : bytes(ctxs) + lo * stride, ctx_index ? n_ctx : n_ctx - lo,
                                           ctx_index ? ctx_index + lo : nullptr, data, soff, slen, first + lo, hi - lo,
                                           fin ? fin + lo : nullptr, digests ? bytes(digests) + lo * dig : nullptr,
-                                          flags & ~BRB_BATCH_ALL_DEVICES, nullptr);
+                                          flags & ~BRB_BATCH_ALL_DEVICES, nullptr, lower, slow);
         });
     const std::vector<uint64_t> rfirst = fl.rebased();
     Staging st;
@@ -542,14 +548,67 @@ int digest_stream_segments(bool sha1, void *ctxs, uint64_t n_ctx, const uint32_t
     const size_t i_d = st.in(data ? bytes(data) + sp.lo : nullptr, sp.bytes());
     const size_t i_o = st.in(sp.off.data(), 8 * nseg);
     const size_t i_l = st.in(slen + k0, 4 * nseg);
+    const size_t i_w = slow ? st.in(slow + k0, nseg) : 0;
     const size_t i_f = st.in(rfirst.data(), 8 * (n + 1));
     const size_t i_n = fin ? st.in(fin, n) : 0;
     const size_t i_g = digests ? st.inout(digests, dig * n) : 0;
     return named.scatter(st.run(s, nullptr, [&] {
-        return launched(brb::launch_digest_stream_segments(sha1, st.dev(i_c), nullptr, st.dev(i_d), st.dev<uint64_t>(i_o),
-                                                           st.dev<uint32_t>(i_l), st.dev<uint64_t>(i_f), n,
-                                                           fin ? st.dev(i_n) : nullptr, digests ? st.dev(i_g) : nullptr, s));
+        return launched(launch(st.dev(i_c), nullptr, st.dev(i_d), st.dev<uint64_t>(i_o), st.dev<uint32_t>(i_l),
+                               slow ? st.dev(i_w) : nullptr, st.dev<uint64_t>(i_f), fin ? st.dev(i_n) : nullptr,
+                               digests ? st.dev(i_g) : nullptr));
     }));
+}
+
+// BRB_MD5LowerTextBatch (md5_lower_kernels.hip): digests[i] and / or strings[i] of key i lower-cased.  BRB_MD5Batch's
+// flags and modes; the host-mode checks -- every list is host memory there -- come before anything runs, and the
+// outputs are fixed-stride rows, so all-devices always splits.  No wave-pair kernel: no fault word.
+int md5_lower_text(const void *data, const uint64_t *offsets, const uint32_t *lengths, uint64_t n, void *digests,
+                   void *strings, unsigned flags, void *stream)
+{
+    t_err.clear();
+    if (n == 0)
+        return BRB_BATCH_OK;
+    if (!offsets || !lengths) {
+        set_err("NULL offsets or lengths");
+        return BRB_BATCH_BADARG;
+    }
+    if (!digests && !strings) {
+        set_err("NULL digests and strings: nothing to write");
+        return BRB_BATCH_BADARG;
+    }
+    if (!items_ok(n) || !flags_ok(flags))
+        return BRB_BATCH_BADARG;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (flags & BRB_BATCH_DEVICE) {
+        if (int ok = device_ok(); ok != BRB_BATCH_OK)
+            return ok;
+        return device_run(brb::launch_md5_lower(bytes(data), offsets, lengths, n, bytes(digests), bytes(strings), s), s, flags);
+    }
+    // host mode: the span of the non-empty keys, rebased to its first byte
+    const Span sp = span_rebase(offsets, lengths, n);
+    if (!sp.ok)
+        return BRB_BATCH_BADARG;
+    if (!data && sp.bytes()) {
+        set_err("NULL data with a key that has bytes");
+        return BRB_BATCH_BADARG;
+    }
+    if (int ok = device_ok(); ok != BRB_BATCH_OK)
+        return ok;
+    if (flags & BRB_BATCH_ALL_DEVICES)   // contiguous key ranges, one per device
+        return brb_host::split_devices(n, [&](int, uint64_t lo, uint64_t hi) {
+            return md5_lower_text(data, offsets + lo, lengths + lo, hi - lo, digests ? bytes(digests) + lo * 16 : nullptr,
+                                  strings ? bytes(strings) + lo * 33 : nullptr, flags & ~BRB_BATCH_ALL_DEVICES, nullptr);
+        });
+    Staging st;
+    const size_t i_d = st.in(data ? bytes(data) + sp.lo : nullptr, sp.bytes());
+    const size_t i_o = st.in(sp.off.data(), 8 * n);
+    const size_t i_l = st.in(lengths, 4 * n);
+    const size_t i_g = digests ? st.out(digests, 16 * n) : 0;
+    const size_t i_s = strings ? st.out(strings, 33 * n) : 0;
+    return st.run(s, nullptr, [&] {
+        return launched(brb::launch_md5_lower(st.dev(i_d), st.dev<uint64_t>(i_o), st.dev<uint32_t>(i_l), n,
+                                              digests ? st.dev(i_g) : nullptr, strings ? st.dev(i_s) : nullptr, s));
+    });
 }
 
 int blowfish_batch(const BRB_BLOWFISH_CTX *ctx, unsigned long *words, uint64_t n_blocks, unsigned flags,
@@ -1544,6 +1603,21 @@ int BRB_MD5UpdateSegmentsBatch(BRB_MD5_CTX *ctxs, uint64_t n_ctx, const uint32_t
 {
     return digest_stream_segments(false, ctxs, n_ctx, ctx_index, data, seg_offsets, seg_lengths, item_first_seg, n, final,
                                   digests, flags, hip_stream);
+}
+
+int BRB_MD5UpdateSegmentsLowerBatch(BRB_MD5_CTX *ctxs, uint64_t n_ctx, const uint32_t *ctx_index, const void *data,
+                                    const uint64_t *seg_offsets, const uint32_t *seg_lengths, const uint8_t *seg_lower,
+                                    const uint64_t *item_first_seg, uint64_t n, const uint8_t *final,
+                                    unsigned char (*digests)[16], unsigned flags, void *hip_stream)
+{
+    return digest_stream_segments(false, ctxs, n_ctx, ctx_index, data, seg_offsets, seg_lengths, item_first_seg, n, final,
+                                  digests, flags, hip_stream, true, seg_lower);
+}
+
+int BRB_MD5LowerTextBatch(const void *data, const uint64_t *offsets, const uint32_t *lengths, uint64_t n,
+                          unsigned char (*digests)[16], char (*strings)[33], unsigned flags, void *hip_stream)
+{
+    return md5_lower_text(data, offsets, lengths, n, digests, strings, flags, hip_stream);
 }
 
 int BrbSha1_UpdateSegmentsBatch(BrbSha1Ctx *ctxs, uint64_t n_ctx, const uint32_t *ctx_index, const void *data,

@@ -55,6 +55,16 @@ hipError_t launch_digest_stream_final(bool sha1, uint8_t *ctxs, const uint32_t *
 hipError_t launch_digest_stream_segments(bool sha1, uint8_t *ctxs, const uint32_t *ctx_index, const uint8_t *data,
                                          const uint64_t *soff, const uint32_t *slen, const uint64_t *first, uint64_t n,
                                          const uint8_t *fin, uint8_t *digests, hipStream_t s);
+// the same for MD5 with segment k taken as BRB_MD5UpdateLowerText when slow[k] != 0 (slow nullptr: every segment)
+hipError_t launch_md5_stream_segments_lower(uint8_t *ctxs, const uint32_t *ctx_index, const uint8_t *data,
+                                            const uint64_t *soff, const uint32_t *slen, const uint8_t *slow,
+                                            const uint64_t *first, uint64_t n, const uint8_t *fin, uint8_t *digests,
+                                            hipStream_t s);
+
+// MD5 of lower-cased keys (md5_lower_kernels.hip): key r = data[offs[r] .. + lens[r]) at any alignment; digests[r]
+// (16 bytes) and / or strings[r] (33 bytes: 32 hex characters and a NUL), rows at any alignment, either may be nullptr
+hipError_t launch_md5_lower(const uint8_t *data, const uint64_t *offs, const uint32_t *lens, uint64_t n, uint8_t *digests,
+                            uint8_t *strings, hipStream_t s);
 
 // MetaDataUnpack of whole packs (metadata_kernels.hip): pack r = data[offs[r] .. + lens[r])
 hipError_t launch_metadata_unpack(const uint8_t *data, const uint64_t *offs, const uint32_t *lens, uint64_t n,

@@ -417,6 +417,25 @@ struct BlockSrcW {
     }
 };
 
+// BRB_MD5UpdateLowerText's byte transform (md5.c:119-123) on four bytes at once: a byte in 'A'..'Z'
+// gets + 0x20, every other byte -- those >= 0x80 too: the reference compares signed char -- stays.
+// h is the byte without its top bit; bit 7 of h + 0x3f is set for h >= 0x41, bit 7 of h + 0x25 for
+// h >= 0x5b; no byte sum exceeds 0xbe, so nothing carries from byte to byte.  A letter's bit 5 is
+// clear, so + 0x20 is | 0x20: six VALU per dword (and, add, sub, bitop3, shift, and-or).
+BRB_DEV uint32_t lower4(uint32_t w)
+{
+    const uint32_t h = w & 0x7f7f7f7fu;
+    const uint32_t t = (h + 0x3f3f3f3fu) & ~(h + 0x25252525u) & ~w;     // bit 7 of every byte 'A'..'Z'
+    return w | ((t >> 2) & 0x20202020u);
+}
+
+BRB_DEV void lower16(uint32_t (&w)[16])
+{
+#pragma unroll
+    for (uint32_t i = 0; i < 16; i++)
+        w[i] = lower4(w[i]);
+}
+
 // The 0x80 end marker of MD5 / SHA-1 padding at byte len % 64 of a (zero-filled) tail block.
 BRB_DEV void add_marker(uint32_t (&w)[16], uint64_t len)
 {

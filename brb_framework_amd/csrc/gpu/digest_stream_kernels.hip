@@ -55,18 +55,6 @@ BRB_DEV void store_words(uint8_t *p, const uint32_t (&w)[W])
         stg(reinterpret_cast<uint32_t *>(p + 4 * k), w[k]);
 }
 
-// lowercase hex of the two low bytes of v, first byte first, high nibble first (md5.c:255-262)
-BRB_DEV uint32_t hex4(uint32_t v)
-{
-    uint32_t r = 0;
-#pragma unroll
-    for (uint32_t c = 0; c < 4; c++) {
-        const uint32_t nib = (v >> (8 * (c >> 1) + ((c & 1) ? 0 : 4))) & 15u;
-        r |= (nib + (nib < 10 ? 0x30u : 0x57u)) << (8 * c);
-    }
-    return r;
-}
-
 // A context is kHdr header words -- the state, then the two counters -- followed by the 64-byte block
 // buffer; `h` below is the header as loaded.
 struct Md5Stream : Md5Words {                       // BRB_MD5_CTX: buf[4], bytes[2], in[16], digest[16], string[64]
@@ -291,13 +279,16 @@ __global__ __launch_bounds__(kBlock) void stream_final_kernel(uint8_t *ctxs, con
 
 // Item i: the segments first[i] .. first[i + 1] - 1 into its context, in order, then Final when fin[i].
 // The shared walk (seg_walk.h) on a funnel seeded from the context.  The counters advance once per segment.
-template <class A>
+// LOWER (BRB_MD5UpdateSegmentsLowerBatch): segment k is lower-cased on the way in when slow[k] != 0, every
+// segment when slow is nullptr; without LOWER slow is not read.
+template <class A, bool LOWER>
 __global__ __launch_bounds__(kBlock) void stream_segments_kernel(uint8_t *ctxs, const uint32_t *__restrict__ ctx_index,
                                                                  const uint8_t *__restrict__ data,
                                                                  const uint64_t *__restrict__ soff,
                                                                  const uint32_t *__restrict__ slen,
                                                                  const uint64_t *__restrict__ first, uint64_t n,
-                                                                 const uint8_t *__restrict__ fin, uint8_t *digests)
+                                                                 const uint8_t *__restrict__ fin, uint8_t *digests,
+                                                                 const uint8_t *__restrict__ slow)
 {
     __shared__ __attribute__((aligned(8192))) uint32_t ring[kBlock / 64][brb_funnel::kRingWords][64];   // 8 KiB per wave
     const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -319,7 +310,7 @@ __global__ __launch_bounds__(kBlock) void stream_segments_kernel(uint8_t *ctxs, 
         return;
     brb_funnel::Funnel<A> f;
     f.seed(&ring[wave][0][lane], A::state(h), in, have);
-    walk.template run<true>(f, beat, [&](uint32_t len) { A::advance(h, len); });
+    walk.template run<true, LOWER>(f, beat, [&](uint32_t len) { A::advance(h, len); }, slow);
 
     f.pump();                                       // fewer than 16 words pending
     uint32_t w[16];
@@ -381,7 +372,8 @@ hipError_t launch_segments(uint8_t *ctxs, const uint32_t *ctx_index, const uint8
 {
     if (n == 0)
         return hipSuccess;
-    stream_segments_kernel<A><<<grid_for(n), kBlock, 0, s>>>(ctxs, ctx_index, data, soff, slen, first, n, fin, digests);
+    stream_segments_kernel<A, false><<<grid_for(n), kBlock, 0, s>>>(ctxs, ctx_index, data, soff, slen, first, n, fin, digests,
+                                                                    nullptr);
     return hipGetLastError();
 }
 
@@ -414,6 +406,18 @@ hipError_t launch_digest_stream_segments(bool sha1, uint8_t *ctxs, const uint32_
 {
     return sha1 ? launch_segments<Sha1Stream>(ctxs, ctx_index, data, soff, slen, first, n, fin, digests, s)
                 : launch_segments<Md5Stream>(ctxs, ctx_index, data, soff, slen, first, n, fin, digests, s);
+}
+
+hipError_t launch_md5_stream_segments_lower(uint8_t *ctxs, const uint32_t *ctx_index, const uint8_t *data,
+                                            const uint64_t *soff, const uint32_t *slen, const uint8_t *slow,
+                                            const uint64_t *first, uint64_t n, const uint8_t *fin, uint8_t *digests,
+                                            hipStream_t s)
+{
+    if (n == 0)
+        return hipSuccess;
+    stream_segments_kernel<Md5Stream, true><<<grid_for(n), kBlock, 0, s>>>(ctxs, ctx_index, data, soff, slen, first, n, fin,
+                                                                           digests, slow);
+    return hipGetLastError();
 }
 
 }  // namespace brb

@@ -113,6 +113,18 @@ BRB_DEV void md5_compress(Md5State &st, const uint32_t (&m)[16])
     st.d += d;
 }
 
+// lowercase hex of the two low bytes of v, first byte first, high nibble first (md5.c:255-262)
+BRB_DEV uint32_t hex4(uint32_t v)
+{
+    uint32_t r = 0;
+#pragma unroll
+    for (uint32_t c = 0; c < 4; c++) {
+        const uint32_t nib = (v >> (8 * (c >> 1) + ((c & 1) ? 0 : 4))) & 15u;
+        r |= (nib + (nib < 10 ? 0x30u : 0x57u)) << (8 * c);
+    }
+    return r;
+}
+
 // MD5 on 16 little-endian message words, as word_funnel.h takes an algorithm
 struct Md5Words {
     using State = Md5State;

@@ -61,25 +61,32 @@ struct SegWalk {
     }
 
     // The rest of the walk, after first().  done(len) once per segment, after its bytes are in.
-    template <bool DIRECT, class F, class Beat, class Done>
-    BRB_DEV void run(F &f, Beat &beat, Done done)
+    // LOWER (BRB_MD5UpdateSegmentsLowerBatch): segment kk is taken as BRB_MD5UpdateLowerText
+    // (Funnel::feed's `lower`) when slow[kk] != 0, every segment when slow is nullptr; the byte is read
+    // once the segment is found, a segment ahead of its bytes like its first block.
+    template <bool DIRECT, bool LOWER = false, class F, class Beat, class Done>
+    BRB_DEV void run(F &f, Beat &beat, Done done, const uint8_t *slow = nullptr)
     {
+        auto low = [&](uint64_t kk) { return LOWER && kk < k1 && (!slow || slow[kk] != 0); };
         brb_io::BlockSrc sb;
         uint32_t lb = 0;
         uint64_t oa = 0, ob = 0;
+        bool wa = low(k);
         while (k < k1) {
             const uint64_t kb = find(k + 1, lb, ob, beat);
+            const bool wb = low(kb);
             if (kb < k1)
                 start(sb, ob, lb, before + la);
-            f.template feed<DIRECT>(sa, la, beat);
+            f.template feed<DIRECT, LOWER>(sa, la, beat, wa);
             done(la);
             before += la;
             if (kb >= k1)
                 break;
             k = find(kb + 1, la, oa, beat);             // sb's length is lb: la is free
+            wa = low(k);
             if (k < k1)
                 start(sa, oa, la, before + lb);
-            f.template feed<DIRECT>(sb, lb, beat);
+            f.template feed<DIRECT, LOWER>(sb, lb, beat, wb);
             done(lb);
             before += lb;
         }

@@ -167,14 +167,19 @@ struct Funnel {
     }
 
     // The piece of `len` bytes behind src (a range that starts nacc bytes early) in 64-byte blocks,
-    // the next one in flight; a beat per block.  DIRECT: whole blocks take put_block.
-    template <bool DIRECT, class Beat>
-    BRB_DEV void feed(brb_io::BlockSrc &src, uint64_t len, Beat &beat)
+    // the next one in flight; a beat per block.  DIRECT: whole blocks take put_block.  LOWER: a piece
+    // with `lower` set is taken as BRB_MD5UpdateLowerText takes it -- its blocks are lower-cased as
+    // fetched, before head() puts the carried bytes in: those are the previous piece's and already
+    // carry that piece's treatment.
+    template <bool DIRECT, bool LOWER = false, class Beat>
+    BRB_DEV void feed(brb_io::BlockSrc &src, uint64_t len, Beat &beat, bool lower = false)
     {
         const uint64_t n = len + nacc;
         for (uint64_t c = 0; c < n; c += 64) {
             uint32_t w[16];
             src.fetch(w);
+            if (LOWER && lower)
+                brb_io::lower16(w);
             if (c == 0)
                 w[0] = head(w[0]);
             const uint64_t left = n - c;

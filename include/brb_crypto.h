@@ -362,6 +362,49 @@ int BrbSha1_UpdateSegmentsBatch(BrbSha1Ctx *ctxs, uint64_t n_ctx, const uint32_t
                                 const uint64_t *item_first_seg, uint64_t n, const uint8_t *final,
                                 uint8_t (*digests)[20], unsigned flags, void *hip_stream);
 
+/* ---- BRB_MD5UpdateLowerText as a batch: case-insensitive keys -----------------------------------
+ * BRB_MD5UpdateLowerText (md5.c:112-132) feeds a context the lower-cased copy of a key: host names,
+ * header names, the case-insensitive half of a composite key.  It is mixed freely with BRB_MD5Update on
+ * one context, and the result is read as ctx.digest or as ctx.string, the 32 hex characters.  MD5 only:
+ * the reference has no SHA-1 counterpart.
+ *   Lower-casing is the reference's: a byte 0x41 .. 0x5A gets + 0x20, every other byte is unchanged --
+ *   bytes >= 0x80 too (the reference compares signed char: 0xC1 .. 0xDA do not move).  A piece of any
+ *   length is accepted, with the meaning of this library's BRB_MD5UpdateLowerText (128-byte steps; the
+ *   reference overruns its stack buffer beyond that).  The counters advance once per key / segment by
+ *   its length, which MD5's additive count makes equal to those 128-byte steps.  Length 0 changes
+ *   nothing (key_sz <= 0 in the reference) and its offset need not be memory.  data is never written.
+ *
+ * BRB_MD5LowerTextBatch, the context-free call for short keys (no 168-byte context is read or written
+ *   per key): key i = data[offsets[i] .. + lengths[i]) at any byte alignment; keys may overlap and may
+ *   be shared.  digests[i] / strings[i] = ctx.digest / ctx.string[0 .. 33) after BRB_MD5Init,
+ *   BRB_MD5UpdateLowerText(key i), BRB_MD5Final: 16 bytes, and 32 lower-case hex characters with their
+ *   NUL (BRB_MD5ToStr's buffer).  digests or strings may be NULL, not both.
+ *   Flags, return codes, hip_stream and the device-mode contract are BRB_MD5Batch's; device mode
+ *   validates nothing beyond NULL pointers, the key count and the flags, and allocates nothing
+ *   (graph-capturable).  BRB_BATCH_HOST returns -1 with a reason, and writes nothing, for: NULL offsets
+ *   or lengths; both outputs NULL; NULL data with a key that has bytes; a key range that wraps; more
+ *   keys than a launch takes; BRB_BATCH_ALL_DEVICES with BRB_BATCH_DEVICE.  Host mode stages the span of
+ *   the non-empty keys in and the given outputs out.  BRB_BATCH_ALL_DEVICES splits the keys into
+ *   contiguous ranges, always: the outputs are fixed-stride rows.  n == 0 returns 1.  No wave-pair
+ *   kernel: BRB_BATCH_FAULT never occurs.  No CPU fallback: without a usable device the call returns 0
+ *   with a LastError and writes nothing.
+ *
+ * BRB_MD5UpdateSegmentsLowerBatch is BRB_MD5UpdateSegmentsBatch with a byte per segment: seg_lower[k] != 0
+ *   takes segment k as BRB_MD5UpdateLowerText, 0 as BRB_MD5UpdateBig; seg_lower == NULL: every segment is
+ *   lower-cased.  seg_lower is indexed like seg_lengths.  Everything BRB_MD5UpdateSegmentsBatch documents
+ *   holds word for word -- the defined part of a context, the untouched digest rows of items not
+ *   finalised, each context named at most once, the host-mode refusals, the staging that travels with the
+ *   item ranges under BRB_BATCH_ALL_DEVICES -- and host mode additionally stages seg_lower over the named
+ *   segment range.  With seg_lower all zero the result is bit for bit BRB_MD5UpdateSegmentsBatch's.  A
+ *   batch BRB_MD5UpdateLowerText on contexts is the one-segment-per-item list with seg_lower == NULL. */
+int BRB_MD5LowerTextBatch(const void *data, const uint64_t *offsets, const uint32_t *lengths, uint64_t n,
+                          unsigned char (*digests)[16], char (*strings)[33], unsigned flags, void *hip_stream);
+int BRB_MD5UpdateSegmentsLowerBatch(BRB_MD5_CTX *ctxs, uint64_t n_ctx, const uint32_t *ctx_index,
+                                    const void *data, const uint64_t *seg_offsets, const uint32_t *seg_lengths,
+                                    const uint8_t *seg_lower, const uint64_t *item_first_seg, uint64_t n,
+                                    const uint8_t *final, unsigned char (*digests)[16], unsigned flags,
+                                    void *hip_stream);
+
 /* Blowfish ECB over n_blocks blocks in place.  A block is the reference's (xl, xr) pair of
  * 64-bit `unsigned long` words (blowfish.c:312, mem_buf.c:1538-1539): words[2i] = xl,
  * words[2i+1] = xr.  The result equals BRB_Blowfish_Encrypt/Decrypt(ctx, &w[2i], &w[2i+1])
