@@ -10,6 +10,12 @@
 //                      last                                (ev_kq_aio_transform.c:212-230, 281-283)
 //   rc4md5_open_kernel READ side + EvAIOReqTransform_RC4_MD5_DataValidate: one pass decrypts the
 //                      frame and feeds the decrypted payload to MD5       (:270-279, :158-184)
+//
+// These three lone-wave kernels are start-up, one call of the per-buffer body in rc4_block.h
+// (crypt_blocks, frame_buffer, open_buffer; rc4_list_kernels.hip calls the same body per buffer of
+// a list) and the state's store.  The wave-pair kernels below split a buffer between two waves and
+// keep their block steps in their own text (DESIGN §4.6a "shared bodies": as helpers they cost time);
+// they share the start-up (rc4_block.h) and, but for the open pair, the prologue pair_start.
 #include <type_traits>
 
 #include "brb_kernels.h"
@@ -23,8 +29,6 @@ namespace {
 using namespace brb_rc4;
 
 constexpr int kWave = 64 * int(kWaves);   // threads per workgroup
-
-// clamp4, wave_max, kXchBytes and decrypt_block: rc4_block.h (shared with rc4_list_kernels.hip)
 
 // SECTOR: outputs through brb_io::SectorSnk (whole aligned 64-byte sectors) instead of Snk.
 // Measured with the first pipelined generator (tools/gpu_rc4_sector.sh, 65 536 x 1500 B, two
@@ -51,13 +55,11 @@ __global__ __launch_bounds__(kWave) void rc4_crypt_kernel(uint8_t *__restrict__ 
     const uint64_t s = uint64_t(blockIdx.x) * kWave + threadIdx.x;
     const bool live = s < n;                     // lanes past n only help with the block loads
     Gen g;
-    g.P.lds = slot;
-    g.P.lw = (threadIdx.x & 63) * 4 + (threadIdx.x >> 6);
+    gen_place(g, slot, lane_word());
     uint8_t *state = nullptr;
     uint64_t off = 0, len = 0, ooff = 0;
     if (live) {
-        state = states + uint64_t(sidx ? sidx[s] : s) * kStateBytes;   // sidx: connection table
-        g.load(state);
+        state = gen_load(g, states, sidx, s);
         off = offs[s];
         len = lens[s];
         ooff = ooffs ? ooffs[s] : off;
@@ -69,35 +71,7 @@ __global__ __launch_bounds__(kWave) void rc4_crypt_kernel(uint8_t *__restrict__ 
         snk.init(out + ooff, len, uint32_t(reinterpret_cast<uintptr_t>(rows)) + threadIdx.x * brb_io::SectorSnk::kRowBytes);
     else
         snk.init(out + ooff, len);
-    const uint64_t nblk = (len + 63) >> 6;
-    const uint32_t nloop = wave_max(uint32_t(nblk));
-    uint32_t c[16];
-    if (nloop)
-        src.fetch(c);
-    for (uint32_t b = 0; b < nloop; b++) {
-        const uint64_t pos = 64ull * b;
-        const bool full = pos + 64 <= len;
-        uint32_t ks[16];
-        if (full) {
-            g.words(ks);
-#pragma unroll
-            for (int i = 0; i < 16; i++)
-                ks[i] ^= c[i];
-        } else if (pos < len) {
-#pragma unroll
-            for (int i = 0; i < 16; i++) {
-                const uint64_t q = pos + 4 * i;
-                if (q < len)
-                    snk.put(c[i] ^ g.next_n(clamp4(len - q)));
-            }
-        }
-        // the next block is taken (and the one after it requested) before this block's stores go
-        // out, so the wait for it never includes them
-        if (b + 1 < nloop)
-            src.fetch(c);
-        if (full)
-            snk.put16(ks);
-    }
+    crypt_blocks(src, snk, g, len, wave_max(uint32_t((len + 63) >> 6)));
     if (live) {
         snk.flush();
         g.store(state);
@@ -116,102 +90,9 @@ __global__ __launch_bounds__(kWave) void rc4md5_frame_kernel(uint8_t *__restrict
     if (s >= n)
         return;
     Gen g;
-    g.P.lds = slot;
-    g.P.lw = (threadIdx.x & 63) * 4 + (threadIdx.x >> 6);
-    uint8_t *state = states + uint64_t(sidx ? sidx[s] : s) * kStateBytes;   // sidx: connection table
-    g.load(state);
-    const uint64_t len = lens[s];
-    const uint64_t F = kHeader + len;            // frame bytes
-    uint8_t *frame = frames + foffs[s];
-
-    // keystream of frame chunks 0..7 (bytes 0..31; chunk 7 = digest[15], NUL, payload[0..1])
-    uint32_t kh[8];
-#pragma unroll
-    for (int k = 0; k < 7; k++)
-        kh[k] = g.next4();
-    kh[7] = g.next_n(clamp4(F - 28));
-
-    brb_io::BlockSrc src;
-    src.init(payload + offs[s], len);
-    Snk snk;                                      // frame bytes 32..F-1
-    snk.init(frame + 32, F > 32 ? F - 32 : 0);
-    Md5State st = md5_iv();
-    const uint64_t nblk = md5_blocks(len), nw = 16 * nblk;
-    uint32_t prev = 0, first = 0;
-    for (uint64_t b = 0; b < nblk; b++) {
-        uint32_t m[16], rw[16];
-        src.fetch(rw);
-        // frame chunks 16b + 7 .. 16b + 22 (payload words 16b .. 16b + 15; word 0 lives in the
-        // header chunk 7): when all of them lie inside the frame, their keystream is one run
-        if (4 * (16 * b + 23) <= F) {
-            uint32_t ks[16];
-            if (b == 0) {
-                uint32_t k15[15];
-                g.words(k15);
-#pragma unroll
-                for (int i = 0; i < 15; i++)
-                    ks[i + 1] = k15[i];
-                ks[0] = 0;
-            } else {
-                g.words(ks);
-            }
-            uint32_t ct[16];
-#pragma unroll
-            for (uint32_t i = 0; i < 16; i++) {
-                const uint64_t w = 16 * b + i;
-                const uint32_t raw = rw[i];
-                if (w == 0)
-                    first = raw;
-                ct[i] = __builtin_amdgcn_alignbit(raw, prev, 16) ^ ks[i];
-                prev = raw;
-                m[i] = raw;
-            }
-            md5_pad_block(m, b, len, nw);
-            if (b == 0) {
-#pragma unroll
-                for (int i = 1; i < 16; i++)
-                    snk.put(ct[i]);
-            } else {
-                snk.put16(ct);
-            }
-        } else {
-#pragma unroll
-            for (uint32_t i = 0; i < 16; i++) {
-                const uint64_t w = 16 * b + i;
-                const uint32_t raw = rw[i];
-                if (w == 0) {
-                    first = raw;
-                } else {
-                    // frame chunk w + 7 = payload bytes 4w - 2 .. 4w + 1
-                    const uint64_t fb = 4 * (w + 7);
-                    if (fb < F)
-                        snk.put(__builtin_amdgcn_alignbit(raw, prev, 16) ^ g.next_n(clamp4(F - fb)));
-                }
-                prev = raw;
-                m[i] = md5_pad_word(raw, w, len, nw);
-            }
-        }
-        md5_compress(st, m);
-    }
-    snk.flush();
-
-    // header: salt (LE unsigned long), "HASH:", digest, NUL, then payload[0..1] in chunk 7
-    const uint64_t salt = salts[s];
-    uint32_t h[8];
-    h[0] = uint32_t(salt);
-    h[1] = uint32_t(salt >> 32);
-    h[2] = 0x48534148u;                           // "HASH"
-    h[3] = 0x3Au | (st.a << 8);                   // ':' + digest[0..2]
-    h[4] = __builtin_amdgcn_alignbit(st.b, st.a, 24);
-    h[5] = __builtin_amdgcn_alignbit(st.c, st.b, 24);
-    h[6] = __builtin_amdgcn_alignbit(st.d, st.c, 24);
-    h[7] = (st.d >> 24) | (first << 16);          // digest[15], NUL, payload[0], payload[1]
-    Snk hs;
-    hs.init(frame, F < 32 ? F : 32);
-#pragma unroll
-    for (int k = 0; k < 8; k++)
-        hs.put(h[k] ^ kh[k]);
-    hs.flush();
+    gen_place(g, slot, lane_word());
+    uint8_t *state = gen_load(g, states, sidx, s);
+    frame_buffer(g, payload + offs[s], lens[s], salts[s], frames + foffs[s]);
     g.store(state);
 }
 
@@ -227,49 +108,10 @@ __global__ __launch_bounds__(kWave) void rc4md5_open_kernel(uint8_t *__restrict_
     if (s >= n)
         return;
     Gen g;
-    g.P.lds = slot;
-    g.P.lw = (threadIdx.x & 63) * 4 + (threadIdx.x >> 6);
-    uint8_t *state = states + uint64_t(sidx ? sidx[s] : s) * kStateBytes;   // sidx: connection table
-    g.load(state);
-    const uint64_t off = offs[s], F = lens[s];
-    brb_io::BlockSrc src;
-    Snk snk;
-    src.init(in + off, F);
-    snk.init(out + (ooffs ? ooffs[s] : off), F);
-
-    // frame block 0 = chunks 0..15; the header is chunks 0..7 (frame bytes 0..31)
-    uint32_t cur[16];
-    decrypt_block(src, snk, g, F, 0, cur);
-    uint32_t ok = 0;
-    if (F >= kHeader) {
-        // payload word w = frame bytes 30 + 4w .. 33 + 4w: the high half of chunk w + 7 and the low
-        // half of chunk w + 8; MD5 block b needs chunks 16b + 7 .. 16b + 23 = frame blocks b, b + 1
-        const uint64_t len = F - kHeader;
-        const uint64_t nblk = md5_blocks(len), nw = 16 * nblk;
-        const uint32_t h2 = cur[2], h3 = cur[3], h4 = cur[4], h5 = cur[5], h6 = cur[6], h7 = cur[7];
-        Md5State st = md5_iv();
-        for (uint64_t b = 0; b < nblk; b++) {
-            uint32_t nxt[16], m[16];
-            decrypt_block(src, snk, g, F, b + 1, nxt);
-#pragma unroll
-            for (int i = 0; i < 16; i++) {
-                const uint32_t lo = i + 7 < 16 ? cur[i + 7] : nxt[i - 9];
-                const uint32_t hi = i + 8 < 16 ? cur[i + 8] : nxt[i - 8];
-                m[i] = __builtin_amdgcn_alignbit(hi, lo, 16);
-            }
-            md5_pad_block(m, b, len, nw);
-            md5_compress(st, m);
-#pragma unroll
-            for (int i = 0; i < 16; i++)
-                cur[i] = nxt[i];
-        }
-        const bool tag = h2 == 0x48534148u && (h3 & 0xFFu) == 0x3Au;   // "HASH:" at 8..12
-        const bool dig = __builtin_amdgcn_alignbit(h4, h3, 8) == st.a && __builtin_amdgcn_alignbit(h5, h4, 8) == st.b &&
-                         __builtin_amdgcn_alignbit(h6, h5, 8) == st.c && __builtin_amdgcn_alignbit(h7, h6, 8) == st.d;
-        ok = tag && dig;
-    }
-    snk.flush();
-    valid[s] = uint8_t(ok);
+    gen_place(g, slot, lane_word());
+    uint8_t *state = gen_load(g, states, sidx, s);
+    const uint64_t off = offs[s];
+    valid[s] = uint8_t(open_buffer(g, in + off, out + (ooffs ? ooffs[s] : off), lens[s]));
     g.store(state);
 }
 
@@ -283,6 +125,27 @@ struct Rc4Mail {
     uint32_t *in_cnt, *in_used, *out_cnt, *out_used;   // this lane's
 };
 
+// The pair kernels' prologue: the mailboxes `mb` (staged, taken, produced, stored blocks per lane)
+// zeroed and the fault word published (pair_sync.h pc_fault_from), for the caller's barrier; waves
+// 0..3 are the keystream waves, wave w4 + 4 is the partner of wave w4.
+struct PairCtx {
+    uint32_t lane, w4;
+    bool partner;
+    Rc4Mail m;
+};
+
+BRB_DEV PairCtx pair_start(uint32_t (&mb)[kWaves][4][64], uint32_t *&fault_at, uint32_t *fault)
+{
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t w4 = wv % kWaves;
+    for (uint32_t i = threadIdx.x; i < kWaves * 4 * 64; i += 2 * kWave)
+        (&mb[0][0][0])[i] = 0;
+    if (threadIdx.x == 0)
+        fault_at = fault;
+    return {lane, w4, wv >= kWaves, {&mb[w4][0][lane], &mb[w4][1][lane], &mb[w4][2][lane], &mb[w4][3][lane]}};
+}
+
 // false after 2^22 sleeps in which the wave's open lanes saw no progress
 template <class F>
 BRB_DEV bool rc4_wait(F blocked)
@@ -295,8 +158,45 @@ BRB_DEV bool rc4_wait(F blocked)
     return false;
 }
 
-// STALL: test option pair_stall (pair_fault.h), a separate instantiation so the product kernel
-// carries no test code.
+// The I/O side of a pair: stage input block bi once block bi - 2 is taken; hand back output block bo
+// once produced.  `stage(c, b)` gets every lane's block b (lanes past their count included: the
+// loads are cooperative); `drain(b)` runs for the lanes whose block b is out.  Returns when every
+// output block is drained (true), or after 2^22 idle sleeps (false: a protocol fault, no hang).
+template <class Stage, class Drain>
+BRB_DEV bool pair_io(const Rc4Mail &m, uint32_t nblk, uint32_t nloop, brb_io::BlockSrcW &src, Stage stage, Drain drain)
+{
+    using brb_line::pc_load;
+    uint32_t bi = 0, bo = 0;
+    for (uint32_t idle = 0; bo < nloop && idle < (1u << 22);) {
+        if (bi < nloop && __builtin_amdgcn_ballot_w64(bi < nblk && pc_load(m.in_used) + 2 <= bi) == 0) {
+            uint32_t c[16];
+            src.fetch(c);
+            stage(c, bi);
+            bi++;
+            idle = 0;
+            continue;
+        }
+        if (__builtin_amdgcn_ballot_w64(bo < nblk && pc_load(m.out_cnt) < bo + 1) == 0) {
+            if (bo < nblk)
+                drain(bo);
+            bo++;
+            idle = 0;
+            continue;
+        }
+        __builtin_amdgcn_s_sleep(1);
+        idle++;
+    }
+    return bo >= nloop;
+}
+
+// STALL (all three pair kernels): test option pair_stall (pair_fault.h) -- the first workgroup's first
+// partner wave never hands a block over, so both waves' bounded waits give up.  A separate
+// instantiation, so the product kernel carries no test code.
+//
+// This kernel's I/O wave is pair_io()'s loop in its own text, and its keystream step is written out:
+// through pair_io(), or with the step as a helper, or both, the pass measured 1.0-1.3 us (1 %) slower,
+// each form against the parent in one interleaved run ("shared bodies").  Keep the loop
+// in step with pair_io() by hand.
 template <bool STALL>
 __global__ __launch_bounds__(2 * kWave) void rc4_crypt_pair_kernel(uint8_t *__restrict__ states, const uint8_t *in,
                                                                    uint8_t *out, const uint64_t *__restrict__ offs,
@@ -308,26 +208,21 @@ __global__ __launch_bounds__(2 * kWave) void rc4_crypt_pair_kernel(uint8_t *__re
     using brb_line::pc_load;
     using brb_line::pc_publish;
     __shared__ __attribute__((aligned(16))) uint8_t slot[kSlotLds];
-    __shared__ uint32_t rin[kWaves][2][16][64];         // staged input blocks, word i of lane l at [.][i][l]
+    __shared__ uint32_t rin[kWaves][2][16][64];         // staged input blocks
     __shared__ uint32_t rout[kWaves][2][16][64];        // produced output blocks
     __shared__ __attribute__((aligned(16))) uint8_t xch[kWaves * kXchBytes];
-    __shared__ uint32_t mb[kWaves][4][64];              // staged, taken, produced, stored (blocks)
-    __shared__ uint32_t *fault_at;                      // pair_sync.h pc_fault_from
-    const uint32_t lane = threadIdx.x & 63;
-    const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const uint32_t w4 = wv % kWaves;
-    for (uint32_t i = threadIdx.x; i < kWaves * 4 * 64; i += 2 * kWave)
-        (&mb[0][0][0])[i] = 0;
-    if (threadIdx.x == 0)
-        fault_at = fault;
+    __shared__ uint32_t mb[kWaves][4][64];
+    __shared__ uint32_t *fault_at;
+    const PairCtx p = pair_start(mb, fault_at, fault);
     __syncthreads();
+    const uint32_t lane = p.lane, w4 = p.w4;
+    const Rc4Mail m = p.m;
     const uint64_t s = uint64_t(blockIdx.x) * kWave + w4 * 64 + lane;
     const bool live = s < n;                           // lanes past n only help with the block loads
     const uint64_t len = live ? lens[s] : 0;
     const uint32_t nblk = uint32_t((len + 63) >> 6);
     const uint32_t nloop = wave_max(nblk);
-    const Rc4Mail m{&mb[w4][0][lane], &mb[w4][1][lane], &mb[w4][2][lane], &mb[w4][3][lane]};
-    if (wv >= kWaves) {
+    if (p.partner) {
         // ---- I/O wave
         const uint64_t off = live ? offs[s] : 0;
         brb_io::BlockSrcW src;
@@ -385,23 +280,19 @@ __global__ __launch_bounds__(2 * kWave) void rc4_crypt_pair_kernel(uint8_t *__re
     // ---- keystream wave (issue priority: its chain is the critical path)
     __builtin_amdgcn_s_setprio(3);
     Gen g;
-    g.P.lds = slot;
-    g.P.lw = lane * 4 + w4;
-    uint8_t *state = live ? states + uint64_t(sidx ? sidx[s] : s) * kStateBytes : nullptr;
-    if (live)
-        g.load(state);
+    gen_place(g, slot, lane * 4 + w4);
+    uint8_t *state = live ? gen_load(g, states, sidx, s) : nullptr;
     for (uint32_t b = 0; b < nloop; b++) {
         if (!rc4_wait([&] { return b < nblk && pc_load(m.in_cnt) < b + 1; }))
             break;                                     // a protocol fault: the I/O wave reports it
         if (b >= nblk)
             continue;
-        uint32_t c[16];
+        uint32_t c[16], o[16];
 #pragma unroll
         for (int i = 0; i < 16; i++)
             c[i] = rin[w4][b & 1][i][lane];
         pc_publish(m.in_used, b + 1);
         const uint64_t pos = 64ull * b;
-        uint32_t o[16];
         if (pos + 64 <= len) {
             uint32_t ks[16];
             g.words(ks);
@@ -442,40 +333,6 @@ __global__ __launch_bounds__(2 * kWave) void rc4_crypt_pair_kernel(uint8_t *__re
 // Earlier forms measured (rocprofv3, 65 536 x 1 530-byte frames): fused frame 128.1 us / open
 // 122.9 us; the MD5 alone on the partner with the keystream wave doing the I/O: frame 127.2 us, open
 // 111.1 us.
-
-// The I/O side of a pair: stage input block bi once block bi - 2 is taken; hand back output block bo
-// once produced.  `stage(c, b)` gets every lane's block b (lanes past their count included: the
-// loads are cooperative); `drain(b)` runs for the lanes whose block b is out.  Returns when every
-// output block is drained (true), or after 2^22 idle sleeps (false: a protocol fault, no hang).
-template <class Stage, class Drain>
-BRB_DEV bool pair_io(const Rc4Mail &m, uint32_t nblk, uint32_t nloop, brb_io::BlockSrcW &src, Stage stage, Drain drain)
-{
-    using brb_line::pc_load;
-    uint32_t bi = 0, bo = 0;
-    for (uint32_t idle = 0; bo < nloop && idle < (1u << 22);) {
-        if (bi < nloop && __builtin_amdgcn_ballot_w64(bi < nblk && pc_load(m.in_used) + 2 <= bi) == 0) {
-            uint32_t c[16];
-            src.fetch(c);
-            stage(c, bi);
-            bi++;
-            idle = 0;
-            continue;
-        }
-        if (__builtin_amdgcn_ballot_w64(bo < nblk && pc_load(m.out_cnt) < bo + 1) == 0) {
-            if (bo < nblk)
-                drain(bo);
-            bo++;
-            idle = 0;
-            continue;
-        }
-        __builtin_amdgcn_s_sleep(1);
-        idle++;
-    }
-    return bo >= nloop;
-}
-
-// STALL (both pair kernels): test option pair_stall, as rc4_crypt_pair_kernel -- the first workgroup's
-// first partner wave stages its blocks but never hands one over, so both waves' bounded waits give up.
 template <bool STALL>
 __global__ __launch_bounds__(2 * kWave) void rc4md5_frame_pair_kernel(uint8_t *__restrict__ states,
                                                                       const uint8_t *__restrict__ payload,
@@ -493,27 +350,22 @@ __global__ __launch_bounds__(2 * kWave) void rc4md5_frame_pair_kernel(uint8_t *_
     __shared__ uint32_t rout[kWaves][2][16][64];
     __shared__ __attribute__((aligned(16))) uint8_t xch[kWaves * kXchBytes];
     __shared__ uint32_t mb[kWaves][4][64];
-    __shared__ uint32_t *fault_at;                      // pair_sync.h pc_fault_from
+    __shared__ uint32_t *fault_at;
     __shared__ uint32_t dg[kWaves][4][64];        // the digests
     __shared__ uint32_t posted[kWaves];
-    const uint32_t lane = threadIdx.x & 63;
-    const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const uint32_t w4 = wv % kWaves;
-    for (uint32_t i = threadIdx.x; i < kWaves * 4 * 64; i += 2 * kWave)
-        (&mb[0][0][0])[i] = 0;
+    const PairCtx p = pair_start(mb, fault_at, fault);
     if (threadIdx.x < kWaves)
         posted[threadIdx.x] = 0;
-    if (threadIdx.x == 0)
-        fault_at = fault;
     __syncthreads();
+    const uint32_t lane = p.lane, w4 = p.w4;
+    const Rc4Mail m = p.m;
     const uint64_t s = uint64_t(blockIdx.x) * kWave + w4 * 64 + lane;
     const bool live = s < n;
     const uint64_t len = live ? lens[s] : 0;
     const uint64_t F = kHeader + len;              // frame bytes
     const uint32_t nblk = live ? uint32_t(md5_blocks(len)) : 0u;
     const uint32_t nloop = wave_max(nblk);
-    const Rc4Mail m{&mb[w4][0][lane], &mb[w4][1][lane], &mb[w4][2][lane], &mb[w4][3][lane]};
-    if (wv >= kWaves) {
+    if (p.partner) {
         // ---- partner: payload blocks in, MD5 (ev_kq_aio_transform.c:218-222), ciphertext out
         brb_io::BlockSrcW src;
         src.init(payload + (live ? offs[s] : 0), len, xch + w4 * kXchBytes);
@@ -580,12 +432,11 @@ __global__ __launch_bounds__(2 * kWave) void rc4md5_frame_pair_kernel(uint8_t *_
     // ---- keystream wave
     __builtin_amdgcn_s_setprio(3);
     Gen g;
-    g.P.lds = slot;
-    g.P.lw = lane * 4 + w4;
-    uint8_t *state = live ? states + uint64_t(sidx ? sidx[s] : s) * kStateBytes : nullptr;
+    gen_place(g, slot, lane * 4 + w4);
+    uint8_t *state = nullptr;
     uint32_t kh[8];                               // keystream of frame chunks 0..7 (the header)
     if (live) {
-        g.load(state);
+        state = gen_load(g, states, sidx, s);
 #pragma unroll
         for (int k = 0; k < 7; k++)
             kh[k] = g.next4();
@@ -602,6 +453,7 @@ __global__ __launch_bounds__(2 * kWave) void rc4md5_frame_pair_kernel(uint8_t *_
         for (int i = 0; i < 16; i++)
             rw[i] = rin[w4][b & 1][i][lane];
         pc_publish(m.in_used, b + 1);
+        // as frame_buffer (rc4_block.h), which puts each chunk as it is made; here they go to the ring
         if (4 * (16 * uint64_t(b) + 23) <= F) {
             uint32_t ks[16];
             if (b == 0) {
@@ -653,7 +505,7 @@ __global__ __launch_bounds__(2 * kWave) void rc4md5_frame_pair_kernel(uint8_t *_
     if (!got)
         st.a = ~st.a;                             // a protocol fault (a wrong header; the partner reports it)
     const uint64_t salt = salts[s];
-    uint32_t h[8];
+    uint32_t h[8];                                // the header, as frame_buffer
     h[0] = uint32_t(salt);
     h[1] = uint32_t(salt >> 32);
     h[2] = 0x48534148u;                           // "HASH"
@@ -671,6 +523,9 @@ __global__ __launch_bounds__(2 * kWave) void rc4md5_frame_pair_kernel(uint8_t *_
     g.store(state);
 }
 
+// This kernel takes none of the shared helpers, not even pair_start and gen_place / gen_load: with
+// those two alone the frame + open step measured 0.9 us above the parent against a spread of 0.5, with
+// more helpers 1.0-1.5 us ("shared bodies").
 template <bool STALL>
 __global__ __launch_bounds__(2 * kWave) void rc4md5_open_pair_kernel(uint8_t *__restrict__ states, const uint8_t *in,
                                                                      uint8_t *out, const uint64_t *__restrict__ offs,
@@ -702,7 +557,7 @@ __global__ __launch_bounds__(2 * kWave) void rc4md5_open_pair_kernel(uint8_t *__
     const bool framed = live && F >= kHeader;
     const uint64_t len = framed ? F - kHeader : 0;
     // frame blocks 0 .. nfb-1: block 0 (the header and payload bytes 0..33), then block b + 1 for
-    // every MD5 block b, as rc4md5_open_kernel
+    // every MD5 block b, as open_buffer (rc4_block.h)
     const uint32_t nmd = framed ? uint32_t(md5_blocks(len)) : 0u;
     const uint32_t nfb = live ? 1 + nmd : 0u;
     const uint32_t nloop = wave_max(nfb);

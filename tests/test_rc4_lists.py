@@ -329,10 +329,15 @@ def test_crypt_split_invariance(brb, torch_dev, coop):
     assert torch_dev.equal(a, b) and torch_dev.equal(a_st, b_st)
 
 
+@pytest.mark.parametrize("pair", [1, 0], ids=["pair", "single"])
 @pytest.mark.parametrize("kind", KINDS)
-def test_list_call_equals_consecutive_single_buffer_calls(brb, orc, torch_dev, kind):
+def test_list_call_equals_consecutive_single_buffer_calls(brb, orc, torch_dev, kind, pair):
     """One list call == k calls of the existing single-buffer entry point over the buffers of rank 0, 1, ...
-    (GPU against GPU), and both equal the oracle."""
+    (GPU against GPU), and both equal the oracle.  The single-buffer calls on both of their routes (test
+    options rc4_pair / rc4md5_pair): the wave pairs, and the lone kernels, which call the list kernels'
+    per-buffer body once (rc4_block.h).  With rc4_pair = 0 and rc4_sector unset the crypt case runs the lone
+    kernel the launcher picks (the sector sink, as the list kernel); rc4_crypt_kernel<false> on the same body
+    is held by test_rc4.py::test_rc4_sector_sink_ragged."""
     torch = torch_dev
     c = _case(brb, orc, kind, 257, 40 + 257)
     to = lambda a: _to(torch, a)
@@ -344,13 +349,14 @@ def test_list_call_equals_consecutive_single_buffer_calls(brb, orc, torch_dev, k
         ks = torch.from_numpy(kn).cuda()
         sub = st[torch.from_numpy(who).cuda()].contiguous()
         o_r, l_r = to(c.offs[kn]), to(c.lens[kn])
-        if kind == "crypt":
-            brb.rc4_crypt_batch(sub, data, o_r, l_r, out=out)
-        elif kind == "open":
-            _, v = brb.rc4md5_open_batch(sub, data, o_r, l_r, out=out)
-            valid[ks] = v
-        else:
-            brb.rc4md5_frame_batch(sub, data, o_r, l_r, to(c.salts[kn]), out, to(c.foffs[kn]))
+        with brb.TestOption("rc4_pair" if kind == "crypt" else "rc4md5_pair", pair):
+            if kind == "crypt":
+                brb.rc4_crypt_batch(sub, data, o_r, l_r, out=out)
+            elif kind == "open":
+                _, v = brb.rc4md5_open_batch(sub, data, o_r, l_r, out=out)
+                valid[ks] = v
+            else:
+                brb.rc4md5_frame_batch(sub, data, o_r, l_r, to(c.salts[kn]), out, to(c.foffs[kn]))
         st[torch.from_numpy(who).cuda()] = sub
     got = c.run(brb, to)
     assert torch.equal(got[0], st) and torch.equal(got[1], out)
