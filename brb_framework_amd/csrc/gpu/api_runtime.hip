@@ -132,11 +132,25 @@ thread_local uint32_t *t_fault_armed = nullptr;       // the word the pair kerne
 // once the stream has drained).  Allocated on the thread's first armed call; nullptr if it cannot be
 // had.  The word is 0 between calls (check() clears it), so arming a call is one thread-local store
 // and nothing runs between the caller and the launch (the bench's events see no host work).
+//
+// That first call may be made while a stream is capturing (a thread new to the library that records
+// a graph).  A page-locked allocation is refused under the global and thread-local capture modes, and
+// the refusal invalidates the capture; it enqueues nothing on any stream, so this one allocation is
+// made with the thread's capture mode exchanged for the relaxed one and the mode is put back.  The
+// exchange runs on the allocating call only.  A word that cannot be had is an error of the call
+// (PairFault::ready), never a launch without a word.
+thread_local hipError_t t_fault_alloc_err = hipSuccess;
+
 uint32_t *alloc_fault_word(uint32_t **slot)
 {
     if (!*slot) {
+        hipStreamCaptureMode mode = hipStreamCaptureModeRelaxed;
+        const bool exchanged = hipThreadExchangeStreamCaptureMode(&mode) == hipSuccess;
         void *p = nullptr;
-        if (hipHostMalloc(&p, 64, hipHostMallocMapped | hipHostMallocCoherent | hipHostMallocPortable) != hipSuccess) {
+        t_fault_alloc_err = hipHostMalloc(&p, 64, hipHostMallocMapped | hipHostMallocCoherent | hipHostMallocPortable);
+        if (exchanged)
+            (void)hipThreadExchangeStreamCaptureMode(&mode);
+        if (t_fault_alloc_err != hipSuccess) {
             (void)hipGetLastError();
             return nullptr;
         }
@@ -164,6 +178,13 @@ PairFault::PairFault(unsigned flags)
 PairFault::~PairFault()
 {
     t_fault_armed = nullptr;
+}
+
+int PairFault::ready() const
+{
+    if (t_fault_armed)
+        return BRB_BATCH_OK;
+    return fail_hip("hipHostMalloc of the thread's wave-pair fault word", t_fault_alloc_err);
 }
 
 int PairFault::check(int rc) const

@@ -31,11 +31,14 @@ inline size_t align_up(size_t x, size_t a)
 // Arms the thread's fault word for one synchronous call (pair_fault.h); check() after the stream
 // has drained turns a fault into BRB_BATCH_FAULT.  A device-mode async call returns before its
 // kernels run: it arms the thread's sticky async word instead, which BRB_CryptoGPU_AsyncFaultCheck
-// reads (and clears) once the caller has synchronised its streams.
+// reads (and clears) once the caller has synchronised its streams.  ready() before the launch:
+// BRB_BATCH_OK, or the call's error when the thread's word could not be allocated -- no call, a
+// captured one least of all, is launched with no word to report into.
 struct PairFault {
     uint32_t *w = nullptr;
     explicit PairFault(unsigned flags);
     ~PairFault();
+    int ready() const;
     PairFault(const PairFault &) = delete;
     PairFault &operator=(const PairFault &) = delete;
     int check(int rc) const;

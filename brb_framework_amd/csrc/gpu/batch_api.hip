@@ -1050,6 +1050,8 @@ int BRB_RC4_CryptBatch(BRB_RC4_State *states, const void *in, void *out, const u
     }
     hipStream_t s = static_cast<hipStream_t>(stream);
     const PairFault pf(flags);                       // pair_fault.h
+    if (int ok = pf.ready(); ok != BRB_BATCH_OK)
+        return ok;
     if (flags & BRB_BATCH_DEVICE)
         return device_run(brb::launch_rc4_crypt(bytes(states), bytes(in), bytes(out), offsets, lengths, n, s), s, flags, &pf);
     const Span sp = span_rebase(offsets, lengths, n);
@@ -1093,6 +1095,8 @@ int BRB_RC4MD5_FrameBatch(BRB_RC4_State *states, const void *payload, const uint
     }
     hipStream_t s = static_cast<hipStream_t>(stream);
     const PairFault pf(flags);                       // pair_fault.h
+    if (int ok = pf.ready(); ok != BRB_BATCH_OK)
+        return ok;
     if (flags & BRB_BATCH_DEVICE)
         return device_run(brb::launch_rc4md5_frame(bytes(states), bytes(payload), offsets, lengths, salts, bytes(frames),
                                                    frame_offsets, n, s),
@@ -1138,6 +1142,8 @@ int BRB_RC4MD5_OpenBatch(BRB_RC4_State *states, const void *frames, void *out, c
     }
     hipStream_t s = static_cast<hipStream_t>(stream);
     const PairFault pf(flags);                       // pair_fault.h
+    if (int ok = pf.ready(); ok != BRB_BATCH_OK)
+        return ok;
     if (flags & BRB_BATCH_DEVICE)
         return device_run(brb::launch_rc4md5_open(bytes(states), bytes(frames), bytes(out), offsets, lengths, n, valid, s), s,
                           flags, &pf);
@@ -1337,6 +1343,8 @@ int BRB_MD5BatchSegments(const void *data, const uint64_t *soff, const uint32_t 
         });
     hipStream_t s = static_cast<hipStream_t>(stream);
     const PairFault pf(flags);                       // pair_fault.h
+    if (int ok = pf.ready(); ok != BRB_BATCH_OK)
+        return ok;
     if (flags & BRB_BATCH_DEVICE)
         return device_run(brb::launch_md5_segments(bytes(data), soff, slen, first, n_rec, bytes(digests), s), s, flags, &pf);
     // host mode: rebase the segment lists to start at 0 and copy the byte span they cover
@@ -1382,6 +1390,8 @@ int BRB_MetaDataUnpackBatch(const void *data, const uint64_t *offs, const uint32
         });
     hipStream_t s = static_cast<hipStream_t>(stream);
     const PairFault pf(flags);                       // pair_fault.h
+    if (int ok = pf.ready(); ok != BRB_BATCH_OK)
+        return ok;
     if (flags & BRB_BATCH_DEVICE)
         return device_run(brb::launch_metadata_unpack(bytes(data), offs, lens, n, info, s), s, flags, &pf);
     // host mode: copy the byte span the packs cover, with the offsets rebased to it
@@ -1421,6 +1431,8 @@ int BRB_MetaDataUnpackItemsBatch(const void *data, const uint64_t *offs, const u
         if (int ok = device_ok(); ok != BRB_BATCH_OK)
             return ok;
         const PairFault pf(flags);                   // pair_fault.h
+        if (int ok = pf.ready(); ok != BRB_BATCH_OK)
+            return ok;
         return device_run(brb::launch_metadata_unpack_items(bytes(data), 0, offs, lens, n, info, ioff, ilen, iid, isub,
                                                             first, added, s),
                           s, flags, &pf);
@@ -1440,6 +1452,8 @@ int BRB_MetaDataUnpackItemsBatch(const void *data, const uint64_t *offs, const u
                                                 first + lo, added + lo, flags & ~BRB_BATCH_ALL_DEVICES, nullptr);
         });
     const PairFault pf(flags);
+    if (int ok = pf.ready(); ok != BRB_BATCH_OK)
+        return ok;
     const uint64_t k0 = fl.k0, nslot = fl.count;
     const std::vector<uint64_t> rfirst = fl.rebased();
     Staging st;

@@ -14,6 +14,9 @@
 //     fault" in BRB_CryptoGPU_LastError();
 //   * a device-mode BRB_BATCH_ASYNC call arms the thread's sticky async word, which
 //     BRB_CryptoGPU_AsyncFaultCheck() reads and clears after the caller has synchronised its streams;
+//     captured in a graph, the kernel node keeps that word, so every replay reports to the thread
+//     that captured the call, which therefore outlives the graph's replays (brb_crypto.h, "GRAPH
+//     CAPTURE");
 //   * a transform batcher round arms its own round word (pair_fault_arm) around its launches and
 //     reads it when the round completes: a set word drops the round (BRB_BATCH_DROPPED, every buffer
 //     delivered as BRB_TRANSFORM_DROPPED), so no wrong plaintext, frame or valid flag is delivered.

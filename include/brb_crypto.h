@@ -154,6 +154,29 @@ void BRB_RC4_Crypt(BRB_RC4_State *state, const unsigned char *inbuf, unsigned ch
  * (pageable or page-locked) in chunks so that copies in both directions overlap the kernels, and
  * returns when the results are in host memory; `hip_stream` is not used. */
 
+/* GRAPH CAPTURE (hipStreamBeginCapture, torch.cuda.graph; tests/test_graph_capture.py): where a call
+ * below says "graph-capturable", this is what it means.
+ *   - Only BRB_BATCH_DEVICE | BRB_BATCH_ASYNC calls may be made on a capturing stream: they enqueue
+ *     their kernels on `hip_stream` and nothing else.  Device mode without ASYNC synchronises the
+ *     stream, host mode copies and synchronises, the MemBuffer calls ignore ASYNC, and a transform
+ *     batcher owns streams and events: each of these on a capturing stream is a caller error and
+ *     invalidates the capture.
+ *   - Each kernel has run once eagerly before its first capture (the runtime loads a code object on a
+ *     kernel's first launch): make one uncaptured call of the same kind first.
+ *   - Fixed when the call is captured: the counts (n, rec_len, n_ctx), every pointer, the kernel the
+ *     launcher chose from them, and the test options.  Read from device memory afresh by every
+ *     replay: the data, offsets, lengths, segment / buffer / item lists, salts, `final` and
+ *     `seg_lower` masks, and the RC4 states and streaming contexts, which advance with every replay
+ *     as they would with every call.  A replay's ranges must lie inside the allocations like a call's.
+ *   - A captured call of a wave-pair kernel (the calls that can return BRB_BATCH_FAULT) reports into
+ *     the async fault word of the thread that CAPTURED it, whichever thread replays the graph: that
+ *     thread calls BRB_CryptoGPU_AsyncFaultCheck() after a replay has been synchronised; a replaying
+ *     thread's own check says nothing about the replay.  The word is allocated on a thread's first
+ *     such call, inside a capture too (the one allocation is made with the thread's capture mode
+ *     exchanged for the relaxed one; if it fails, the call returns 0 with the reason and launches
+ *     nothing).  It is freed when that thread exits or calls BRB_CryptoGPU_ThreadCleanup(): the
+ *     capturing thread does neither while the graph can still be replayed. */
+
 /* MD5 of n_rec records of rec_len bytes each, stored back to back: record i is
  * data[i*rec_len .. (i+1)*rec_len).  digests[i] = BRB_MD5Init/Update/Final of record i. */
 int BRB_MD5BatchFixed(const void *data, uint32_t rec_len, uint64_t n_rec,
@@ -293,7 +316,8 @@ int BrbSha1_Batch(const void *data, const uint64_t *offsets, const uint32_t *len
  * SHA-1 Final = BrbSha1_Final: 20 big-endian bytes to digests[i] (required), the whole context zeroed.
  * Flags, return codes, hip_stream and the device-mode contract are BRB_MD5Batch's.  n == 0 returns 1.
  * BRB_BATCH_DEVICE (optionally BRB_BATCH_ASYNC): ctxs, ctx_index, data, offsets, lengths and digests
- * are device memory, ctxs 4-byte aligned; nothing is allocated (graph-capturable) and nothing is
+ * are device memory, ctxs 4-byte aligned; nothing is allocated (with ASYNC graph-capturable: GRAPH
+ * CAPTURE above) and nothing is
  * validated beyond NULL pointers and the item count.  BRB_BATCH_HOST returns -1 with a reason, and
  * writes nothing, for: a NULL required pointer (ctx_index may be NULL; data may be NULL only when every
  * length is 0; MD5's digests may be NULL); ctx_index[i] >= n_ctx; a NULL ctx_index with n > n_ctx; a
@@ -344,7 +368,8 @@ int BrbSha1_FinalBatch(BrbSha1Ctx *ctxs, uint64_t n_ctx, const uint32_t *ctx_ind
  *   finalised and digests is not used.  n == 0 returns 1.
  * Flags, return codes, hip_stream and the device-mode contract are BRB_MD5UpdateBatch's.
  * BRB_BATCH_DEVICE validates nothing beyond NULL pointers, the item count and the flags; ctxs is 4-byte
- * aligned; nothing is allocated (graph-capturable).  BRB_BATCH_HOST returns -1 with a reason, and writes
+ * aligned; nothing is allocated (with ASYNC graph-capturable: GRAPH CAPTURE above).  BRB_BATCH_HOST
+ * returns -1 with a reason, and writes
  * nothing, for: a NULL required pointer (data may be NULL only when every named segment is empty;
  * ctx_index, final and MD5's digests may be NULL); ctx_index[i] >= n_ctx; a NULL ctx_index with
  * n > n_ctx; a context named twice; item_first_seg that decreases; a segment range that wraps; more
@@ -381,7 +406,8 @@ int BrbSha1_UpdateSegmentsBatch(BrbSha1Ctx *ctxs, uint64_t n_ctx, const uint32_t
  *   NUL (BRB_MD5ToStr's buffer).  digests or strings may be NULL, not both.
  *   Flags, return codes, hip_stream and the device-mode contract are BRB_MD5Batch's; device mode
  *   validates nothing beyond NULL pointers, the key count and the flags, and allocates nothing
- *   (graph-capturable).  BRB_BATCH_HOST returns -1 with a reason, and writes nothing, for: NULL offsets
+ *   (with ASYNC graph-capturable: GRAPH CAPTURE above).  BRB_BATCH_HOST returns -1 with a reason, and
+ *   writes nothing, for: NULL offsets
  *   or lengths; both outputs NULL; NULL data with a key that has bytes; a key range that wraps; more
  *   keys than a launch takes; BRB_BATCH_ALL_DEVICES with BRB_BATCH_DEVICE.  Host mode stages the span of
  *   the non-empty keys in and the given outputs out.  BRB_BATCH_ALL_DEVICES splits the keys into
@@ -521,7 +547,8 @@ int BRB_RC4MD5_OpenBatch(BRB_RC4_State *states, const void *frames, void *out, c
  * keep their values.
  * Flags, return codes and hip_stream as BRB_RC4_CryptBatch.  BRB_BATCH_DEVICE (optionally
  * BRB_BATCH_ASYNC): every pointer is device memory, states are 4-byte aligned, nothing is allocated
- * (graph-capturable) and nothing is validated beyond NULL pointers, the stream count and the flags.
+ * (with ASYNC graph-capturable: GRAPH CAPTURE above) and nothing is validated beyond NULL pointers, the
+ * stream count and the flags.
  * BRB_BATCH_HOST returns -1 with a reason, and writes nothing, for: a NULL required pointer; a
  * stream_first_buf that decreases; an offset + length (+ 30 for frames) that wraps; more streams or
  * buffers than a launch takes; BRB_BATCH_ALL_DEVICES with BRB_BATCH_DEVICE.  Host mode stages the
@@ -733,14 +760,16 @@ int BRB_CryptoGPU_GetDevice(void);
 /* Frees the calling thread's host-mode scratch (device workspaces, streams, events) now instead of
  * at thread exit.  Call it with no batch call of this thread running.  If the thread made
  * device-mode BRB_BATCH_ASYNC calls of wave-pair kernels, their devices are synchronised first
- * (hipDeviceSynchronize), since those kernels may still write the thread's fault word. */
+ * (hipDeviceSynchronize), since those kernels may still write the thread's fault word.  Not while a
+ * graph in which this thread captured such a call can still be replayed (GRAPH CAPTURE above). */
 void BRB_CryptoGPU_ThreadCleanup(void);
 /* Last error of the calling thread ("" if none). */
 const char *BRB_CryptoGPU_LastError(void);
 /* Wave-pair faults of the calling thread's device-mode BRB_BATCH_ASYNC calls: 1 if none of the
  * wave-pair kernels they enqueued since the last check reported a protocol fault, BRB_BATCH_FAULT
  * (-4) if one did (reason in LastError; the report is cleared).  Call it after synchronising the
- * streams those calls used: a kernel still running has not reported yet. */
+ * streams those calls used: a kernel still running has not reported yet.  Replays of a graph count as
+ * calls of the thread that captured them (GRAPH CAPTURE above). */
 int BRB_CryptoGPU_AsyncFaultCheck(void);
 /* Page-lock [p, p + len) for the GPU (hipHostRegister, mapped) so that zero-copy batchers can read
  * it: 1 = done, 0 = no device / HIP error (LastError), -1 = bad arguments.  Unregister takes the
