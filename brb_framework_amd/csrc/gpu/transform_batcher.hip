@@ -15,6 +15,10 @@
 // the list kernels (rc4_list_kernels.hip), its buffers in submission order, so the round is one
 // launch per direction -- READ, then WRITE -- and a state is loaded and stored once per round.
 //
+// Both are one plan (round_plan.h: a round's launches and the metadata each reads, host arithmetic
+// only) and one launch table (where(), launch_groups()); a sub-round group is a list group whose
+// streams hold one buffer each.
+//
 // Zero-copy rounds (BRB_BATCHER_ZERO_COPY): the callers' buffers are page-locked, Read/Write keep a
 // reference instead of copying them into the arena, the kernels read them over PCIe and write the
 // results straight into the page-locked output arena.  The copy mode spent ~60 % of a round in the
@@ -32,35 +36,22 @@
 #include "brb_crypto.h"
 #include "brb_kernels.h"
 #include "host_pipe.h"
+#include "round_plan.h"
 
 using brb_api::DeviceGuard;
 using brb_api::fail_hip;
 using brb_api::set_err;
+using brb_plan::Group;
+using brb_plan::Item;
+using brb_plan::up;
 
 namespace {
 
 constexpr uint32_t kHdr = BRB_RC4MD5_HEADER;
 constexpr size_t kAlign = 256;    // arenas
-// metadata bytes budgeted per buffer: 32 of arrays + up to 40 of padding + valid.  Connection lists
-// (BRB_BATCHER_CONN_LISTS): 28 of per-buffer arrays + 12 per stream (sidx and `first`; a group has no
-// more streams than buffers) + valid = 41; the 8 bytes of each group's extra `first` entry and the
-// padding of its six arrays (two groups) come out of meta_cap's fixed 4096.
+// metadata bytes budgeted per buffer: a round of max_items buffers needs at most 41 each plus 32,
+// which tests/test_round_plan_cpu.py checks against meta_cap's formula (Create) at the extremes
 constexpr size_t kMetaItem = 80;
-
-inline size_t up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-
-struct Item {
-    uint32_t conn;
-    int op;
-    uint64_t in_off;  // copy mode: offset in the input arena; zero-copy: device address of the buffer
-    uint32_t in_len;
-    uint64_t out_off;
-    uint32_t out_len;
-    uint64_t salt;
-    uint32_t round;   // sub-round
-    uint32_t epoch;   // the connection's key epoch at submission (BRB_TransformBatcher::epoch)
-    uint32_t pos;     // connection lists: the buffer's index in its direction's group (list order)
-};
 
 // Page-locked host ranges registered through BRB_CryptoGPU_HostRegister: host base, length, the
 // device address of the base.  Sorted by host base.
@@ -179,8 +170,8 @@ struct Round {
     std::atomic<uint64_t> n_slots{0}, in_used{0}, out_used{0};
     std::atomic<uint64_t> gen{0};          // new value at every reset: invalidates threads' chunks
     std::vector<Item> items;               // the launched round's buffers, in slot order
-    // filled by launch_round, read by deliver_round
-    std::vector<int64_t> group_of;         // (sub-round, op) -> group
+    // filled by enqueue_round, read by deliver_round
+    brb_plan::Plan plan;
     std::vector<size_t> group_valid;       // group -> offset of its valid flags in h_meta
     hipEvent_t done = nullptr;
     hipEvent_t ev_h2d = nullptr, ev_kern = nullptr;   // pipelined: inputs landed, kernels finished
@@ -687,146 +678,42 @@ static size_t collect(BRB_TransformBatcher *b, Round &R, std::vector<Item> *stal
     return R.items.size();
 }
 
-// Enqueues round R on the batcher's stream: metadata, H2D, the kernels, D2H, then R.done.  Nothing
-// waits here; the stream keeps rounds (and so every connection's RC4 stream) in order.  *started is
-// set once the first copy has been enqueued.
-static int enqueue_round(BRB_TransformBatcher *b, Round &R, bool *started)
+// Where the kernels of a direction read and write, and where the host finds the results: one choice
+// by (zero-copy, algo, op), taken by launch_groups() and by deliver_round().
+struct Where {
+    enum Kind { CRYPT, FRAME, OPEN } kind;
+    uint8_t *in, *out, *valid;   // device bases of the inputs, the outputs and the valid flags
+    const uint8_t *h_out;        // the host's view of `out` (copy mode: once the D2H copies have landed)
+    bool at_out_off;             // outputs lie at Item::out_off (the kernel takes ooffs), else they mirror in_off
+    bool has_valid() const { return kind == OPEN; }
+    const uint8_t *result(const Item &it) const { return h_out + (at_out_off ? it.out_off : it.in_off); }
+};
+
+static Where where(const BRB_TransformBatcher *b, const Round &R, int op)
 {
-    hipError_t e;
-    // arena bytes past the last successful reservation belong to failed ones: not copied
-    const uint64_t in_used = std::min<uint64_t>(R.in_used, b->cap), out_used = std::min<uint64_t>(R.out_used, b->out_cap);
-    // sub-round of every item: its rank among the same connection's items in the same direction
-    std::vector<uint32_t> seen(size_t(2) * b->max_conns, 0);
-    uint32_t rounds = 0;
-    for (Item &it : R.items) {
-        it.round = seen[size_t(it.op) * b->max_conns + it.conn]++;
-        rounds = std::max(rounds, it.round + 1);
+    Where w;
+    w.kind = b->algo == BRB_CRYPTO_FUNC_RC4 ? Where::CRYPT : op == BRB_CRYPTO_OP_WRITE ? Where::FRAME : Where::OPEN;
+    if (b->zc) {
+        // inputs read in place over PCIe (offs are relative to out_dev), outputs written into the
+        // page-locked output arena
+        w.in = w.out = reinterpret_cast<uint8_t *>(R.out_dev);
+        w.valid = reinterpret_cast<uint8_t *>(R.meta_dev);
+        w.h_out = R.h_out;
+    } else {
+        // an open decrypts in place in the input arena, which is copied back with the frames in it
+        w.in = R.d_in;
+        w.out = w.kind == Where::OPEN ? R.d_in : R.d_out;
+        w.valid = R.d_meta;
+        w.h_out = w.kind == Where::OPEN ? R.h_in : R.h_out;
     }
-    // metadata: per (sub-round, op) a contiguous group: sidx u32[], offs u64[], lens u32[], ooffs u64[], salts u64[]
-    // connection lists: per op one group: sidx u32[streams], first u64[streams + 1], then the per-buffer arrays
-    struct Group {
-        int op;
-        uint32_t count;     // buffers
-        size_t o_sidx, o_offs, o_lens, o_ooffs, o_salts;
-        uint32_t streams;   // connection lists: (direction, connection) streams of the group
-        size_t o_first;
-    };
-    std::vector<Group> groups;
-    R.group_of.assign(b->lists ? 2 : size_t(rounds) * 2, -1);
-    size_t m = 0;
-    for (int op = 0; b->lists && op < 2; op++) {   // READ first, then WRITE
-        // streams in order of first appearance, a stream's buffers in submission order
-        uint32_t *sid = seen.data() + size_t(op) * b->max_conns;   // connection -> stream + 1
-        std::fill(sid, sid + b->max_conns, 0u);
-        std::vector<uint32_t> conns;
-        std::vector<uint64_t> next;        // stream -> its buffer count, then the next free buffer index
-        uint32_t c = 0;
-        for (const Item &it : R.items) {
-            if (it.op != op)
-                continue;
-            if (!sid[it.conn]) {
-                conns.push_back(it.conn);
-                next.push_back(0);
-                sid[it.conn] = uint32_t(conns.size());
-            }
-            ++next[sid[it.conn] - 1];
-            ++c;
-        }
-        if (!c)
-            continue;
-        const size_t ns = conns.size();
-        Group g{op, c, 0, 0, 0, 0, 0, uint32_t(ns), 0};
-        g.o_sidx = m;
-        m = up(m + 4 * ns, 8);
-        g.o_first = m;
-        m = up(m + 8 * (ns + 1), 8);
-        g.o_offs = m;
-        m = up(m + 8 * size_t(c), 8);
-        g.o_lens = m;
-        m = up(m + 4 * size_t(c), 8);
-        g.o_ooffs = m;
-        m = up(m + 8 * size_t(c), 8);
-        g.o_salts = m;
-        m = up(m + 8 * size_t(c), 8);
-        if (m > b->meta_cap) {
-            set_err("metadata overflow");
-            return BRB_BATCH_NOT_DONE;
-        }
-        uint64_t *first = reinterpret_cast<uint64_t *>(R.h_meta + g.o_first);
-        uint64_t at = 0;
-        for (size_t i = 0; i < ns; i++) {
-            reinterpret_cast<uint32_t *>(R.h_meta + g.o_sidx)[i] = uint32_t(op) * b->max_conns + conns[i];
-            first[i] = at;
-            at += next[i];
-            next[i] = first[i];
-        }
-        first[ns] = at;
-        for (Item &it : R.items) {
-            if (it.op != op)
-                continue;
-            const uint64_t k = next[sid[it.conn] - 1]++;
-            it.pos = uint32_t(k);
-            reinterpret_cast<uint64_t *>(R.h_meta + g.o_offs)[k] = b->zc ? it.in_off - uint64_t(R.out_dev) : it.in_off;
-            reinterpret_cast<uint32_t *>(R.h_meta + g.o_lens)[k] = it.in_len;
-            reinterpret_cast<uint64_t *>(R.h_meta + g.o_ooffs)[k] = it.out_off;
-            reinterpret_cast<uint64_t *>(R.h_meta + g.o_salts)[k] = it.salt;
-        }
-        R.group_of[op] = int64_t(groups.size());
-        groups.push_back(g);
-    }
-    for (uint32_t r = 0; !b->lists && r < rounds; r++)
-        for (int op = 0; op < 2; op++) {
-            uint32_t c = 0;
-            for (const Item &it : R.items)
-                c += it.round == r && it.op == op;
-            if (!c)
-                continue;
-            Group g{op, c, 0, 0, 0, 0, 0};
-            g.o_sidx = m;
-            m = up(m + 4 * size_t(c), 8);
-            g.o_offs = m;
-            m = up(m + 8 * size_t(c), 8);
-            g.o_lens = m;
-            m = up(m + 4 * size_t(c), 8);
-            g.o_ooffs = m;
-            m = up(m + 8 * size_t(c), 8);
-            g.o_salts = m;
-            m = up(m + 8 * size_t(c), 8);
-            if (m > b->meta_cap) {
-                set_err("metadata overflow");
-                return BRB_BATCH_NOT_DONE;
-            }
-            uint32_t k = 0;
-            for (const Item &it : R.items) {
-                if (it.round != r || it.op != op)
-                    continue;
-                reinterpret_cast<uint32_t *>(R.h_meta + g.o_sidx)[k] = uint32_t(op) * b->max_conns + it.conn;
-                // zero-copy: kernels address input buffers as out_dev + (device address - out_dev)
-                reinterpret_cast<uint64_t *>(R.h_meta + g.o_offs)[k] = b->zc ? it.in_off - uint64_t(R.out_dev) : it.in_off;
-                reinterpret_cast<uint32_t *>(R.h_meta + g.o_lens)[k] = it.in_len;
-                reinterpret_cast<uint64_t *>(R.h_meta + g.o_ooffs)[k] = it.out_off;
-                reinterpret_cast<uint64_t *>(R.h_meta + g.o_salts)[k] = it.salt;
-                ++k;
-            }
-            R.group_of[size_t(r) * 2 + op] = int64_t(groups.size());
-            groups.push_back(g);
-        }
-    // valid flags: one byte per item of each read group, after the metadata
-    const size_t o_valid = m;
-    if (o_valid + R.items.size() > b->meta_cap) {
-        set_err("metadata overflow");
-        return BRB_BATCH_NOT_DONE;
-    }
-    hipStream_t s = b->stream;
-    const bool split = b->s_h2d != nullptr;
-    // the arena's previous round was delivered (its done event waited on) before it was refilled
-    hipStream_t sh = split ? b->s_h2d : s;
-    *started = true;
-    if ((!b->zc && (e = hipMemcpyAsync(R.d_in, R.h_in, in_used, hipMemcpyHostToDevice, sh)) != hipSuccess) ||
-        (e = hipMemcpyAsync(R.d_meta, R.h_meta, m, hipMemcpyHostToDevice, sh)) != hipSuccess)
-        return fail_hip("hipMemcpyAsync H2D", e);
-    if (split && ((e = hipEventRecord(R.ev_h2d, sh)) != hipSuccess || (e = hipStreamWaitEvent(s, R.ev_h2d, 0)) != hipSuccess))
-        return fail_hip("H2D event", e);
+    w.at_out_off = b->zc || w.kind == Where::FRAME;
+    return w;
+}
+
+// Launches the round's groups in plan order on the batcher's stream.  *vpos: in, the offset of the
+// round's valid flags; out, the end of those the open groups took (R.group_valid: where each starts).
+static int launch_groups(BRB_TransformBatcher *b, Round &R, size_t *vpos)
+{
     // the round's pair kernels report a protocol fault into R.fault (pair_fault.h); the word's last
     // reader was this round's previous delivery, so no kernel still writes it
     __atomic_store_n(R.fault, 0u, __ATOMIC_RELAXED);
@@ -835,63 +722,73 @@ static int enqueue_round(BRB_TransformBatcher *b, Round &R, bool *started)
         explicit Arm(uint32_t *w) : prev(brb::pair_fault_arm(w)) {}
         ~Arm() { brb::pair_fault_arm(prev); }
     } arm(R.fault);
-    uint8_t *zbase = reinterpret_cast<uint8_t *>(R.out_dev);   // zero-copy: inputs and outputs
-    uint8_t *zvalid = reinterpret_cast<uint8_t *>(R.meta_dev);
-    size_t vpos = o_valid;
-    R.group_valid.assign(groups.size(), 0);
-    for (size_t gi = 0; gi < groups.size(); gi++) {
-        const Group &g = groups[gi];
+    const Where by_op[2] = {where(b, R, 0), where(b, R, 1)};
+    hipStream_t s = b->stream;
+    R.group_valid.assign(R.plan.groups.size(), 0);
+    for (size_t gi = 0; gi < R.plan.groups.size(); gi++) {
+        const Group &g = R.plan.groups[gi];
+        const Where &w = by_op[g.op];
         const uint32_t *sidx = reinterpret_cast<const uint32_t *>(R.d_meta + g.o_sidx);
+        const uint64_t *first = reinterpret_cast<const uint64_t *>(R.d_meta + g.o_first);
         const uint64_t *offs = reinterpret_cast<const uint64_t *>(R.d_meta + g.o_offs);
         const uint32_t *lens = reinterpret_cast<const uint32_t *>(R.d_meta + g.o_lens);
         const uint64_t *ooffs = reinterpret_cast<const uint64_t *>(R.d_meta + g.o_ooffs);
         const uint64_t *salts = reinterpret_cast<const uint64_t *>(R.d_meta + g.o_salts);
+        const uint64_t *oo = w.at_out_off ? ooffs : nullptr;   // crypt and open: nullptr = out mirrors in
         if (int64_t(gi) == b->fault_launch)
             return fail_hip("kernel launch (injected fault)", hipErrorLaunchFailure);
-        if (b->lists) {
-            // the launches below with a buffer list per connection (rc4_list_kernels.hip)
-            const uint64_t *first = reinterpret_cast<const uint64_t *>(R.d_meta + g.o_first);
-            if (b->algo == BRB_CRYPTO_FUNC_RC4) {
-                e = b->zc ? brb::launch_rc4_crypt_list(b->d_states, zbase, zbase, offs, lens, first, g.streams, s, sidx, ooffs)
-                          : brb::launch_rc4_crypt_list(b->d_states, R.d_in, R.d_out, offs, lens, first, g.streams, s, sidx);
-            } else if (g.op == BRB_CRYPTO_OP_WRITE) {
-                e = b->zc ? brb::launch_rc4md5_frame_list(b->d_states, zbase, offs, lens, salts, zbase, ooffs, first,
-                                                          g.streams, s, sidx)
-                          : brb::launch_rc4md5_frame_list(b->d_states, R.d_in, offs, lens, salts, R.d_out, ooffs, first,
-                                                          g.streams, s, sidx);
-            } else {
-                R.group_valid[gi] = vpos;
-                e = b->zc ? brb::launch_rc4md5_open_list(b->d_states, zbase, zbase, offs, lens, first, g.streams,
-                                                         zvalid + vpos, s, sidx, ooffs)
-                          : brb::launch_rc4md5_open_list(b->d_states, R.d_in, R.d_in, offs, lens, first, g.streams,
-                                                         R.d_meta + vpos, s, sidx);
-                vpos += g.count;
-            }
-        } else if (b->zc) {
-            // inputs read in place over PCIe, outputs written into the page-locked output arena
-            if (b->algo == BRB_CRYPTO_FUNC_RC4) {
-                e = brb::launch_rc4_crypt(b->d_states, zbase, zbase, offs, lens, g.count, s, sidx, ooffs, true);
-            } else if (g.op == BRB_CRYPTO_OP_WRITE) {
-                e = brb::launch_rc4md5_frame(b->d_states, zbase, offs, lens, salts, zbase, ooffs, g.count, s, sidx);
-            } else {
-                R.group_valid[gi] = vpos;
-                e = brb::launch_rc4md5_open(b->d_states, zbase, zbase, offs, lens, g.count, zvalid + vpos, s, sidx, ooffs);
-                vpos += g.count;
-            }
-        } else if (b->algo == BRB_CRYPTO_FUNC_RC4) {
-            // the output arena mirrors the input arena for RC4 (same offsets, same lengths)
-            e = brb::launch_rc4_crypt(b->d_states, R.d_in, R.d_out, offs, lens, g.count, s, sidx);
-        } else if (g.op == BRB_CRYPTO_OP_WRITE) {
-            e = brb::launch_rc4md5_frame(b->d_states, R.d_in, offs, lens, salts, R.d_out, ooffs, g.count, s, sidx);
-        } else {
-            // decrypt in place in the input arena, then the frames are copied out with it
-            R.group_valid[gi] = vpos;
-            e = brb::launch_rc4md5_open(b->d_states, R.d_in, R.d_in, offs, lens, g.count, R.d_meta + vpos, s, sidx);
-            vpos += g.count;
+        hipError_t e;
+        switch (w.kind) {
+        case Where::CRYPT:
+            e = b->lists ? brb::launch_rc4_crypt_list(b->d_states, w.in, w.out, offs, lens, first, g.streams, s, sidx, oo)
+                         : brb::launch_rc4_crypt(b->d_states, w.in, w.out, offs, lens, g.count, s, sidx, oo);
+            break;
+        case Where::FRAME:
+            e = b->lists ? brb::launch_rc4md5_frame_list(b->d_states, w.in, offs, lens, salts, w.out, ooffs, first,
+                                                         g.streams, s, sidx)
+                         : brb::launch_rc4md5_frame(b->d_states, w.in, offs, lens, salts, w.out, ooffs, g.count, s, sidx);
+            break;
+        default:
+            R.group_valid[gi] = *vpos;
+            e = b->lists ? brb::launch_rc4md5_open_list(b->d_states, w.in, w.out, offs, lens, first, g.streams,
+                                                        w.valid + *vpos, s, sidx, oo)
+                         : brb::launch_rc4md5_open(b->d_states, w.in, w.out, offs, lens, g.count, w.valid + *vpos, s, sidx, oo);
+            *vpos += g.count;
         }
         if (e != hipSuccess)
             return fail_hip("kernel launch", e);
     }
+    return BRB_BATCH_OK;
+}
+
+// Enqueues round R on the batcher's stream: plan and metadata, H2D, the kernels, D2H, then R.done.
+// Nothing waits here; the stream keeps rounds (and so every connection's RC4 stream) in order.
+// *started is set once the first copy has been enqueued.
+static int enqueue_round(BRB_TransformBatcher *b, Round &R, bool *started)
+{
+    hipError_t e;
+    // zero-copy: kernels address input buffers as out_dev + (device address - out_dev)
+    if (!brb_plan::plan_round(R.items, b->max_conns, b->lists, b->zc, uint64_t(R.out_dev), R.h_meta, b->meta_cap, &R.plan)) {
+        set_err("metadata overflow");
+        return BRB_BATCH_NOT_DONE;
+    }
+    // arena bytes past the last successful reservation belong to failed ones: not copied
+    const uint64_t in_used = std::min<uint64_t>(R.in_used, b->cap), out_used = std::min<uint64_t>(R.out_used, b->out_cap);
+    // valid flags: one byte per item of each open group, after the metadata
+    const size_t o_valid = R.plan.o_valid;
+    hipStream_t s = b->stream;
+    const bool split = b->s_h2d != nullptr;
+    // the arena's previous round was delivered (its done event waited on) before it was refilled
+    hipStream_t sh = split ? b->s_h2d : s;
+    *started = true;
+    if ((!b->zc && (e = hipMemcpyAsync(R.d_in, R.h_in, in_used, hipMemcpyHostToDevice, sh)) != hipSuccess) ||
+        (e = hipMemcpyAsync(R.d_meta, R.h_meta, o_valid, hipMemcpyHostToDevice, sh)) != hipSuccess)
+        return fail_hip("hipMemcpyAsync H2D", e);
+    if (split && ((e = hipEventRecord(R.ev_h2d, sh)) != hipSuccess || (e = hipStreamWaitEvent(s, R.ev_h2d, 0)) != hipSuccess))
+        return fail_hip("H2D event", e);
+    size_t vpos = o_valid;
+    if (int rc = launch_groups(b, R, &vpos); rc != BRB_BATCH_OK)
+        return rc;
     hipStream_t sd = split ? b->s_d2h : s;
     if (split && ((e = hipEventRecord(R.ev_kern, s)) != hipSuccess || (e = hipStreamWaitEvent(sd, R.ev_kern, 0)) != hipSuccess))
         return fail_hip("kernel event", e);
@@ -938,8 +835,8 @@ static int launch_round(BRB_TransformBatcher *b, Round &R, BRB_TransformDone don
     return BRB_BATCH_DROPPED;
 }
 
-// Waits for round R and hands every result back in submission order; the k-th read item of a
-// group has valid flag k of that group.  Returns the number of buffers delivered, or -1 when the
+// Waits for round R and hands every result back in submission order; a buffer's valid flag is flag
+// Item::pos of its group.  Returns the number of buffers delivered, or -1 when the
 // round failed on the device (dropped: drop_round's callbacks, its connections poisoned; reason in
 // LastError).  Buffers of connections poisoned after R was launched come back
 // BRB_TRANSFORM_DROPPED and are counted in *n_stale.
@@ -967,12 +864,9 @@ static int64_t deliver_round(BRB_TransformBatcher *b, Round &R, BRB_TransformDon
         drop_round(R, done, user);
         return -1;
     }
-    std::vector<uint32_t> next_in_group(R.group_valid.size(), 0);
+    const Where by_op[2] = {where(b, R, 0), where(b, R, 1)};
     int64_t delivered = 0;
     for (const Item &it : R.items) {
-        // connection lists: one group per direction, valid flags in list order (Item::pos)
-        const int64_t gi = R.group_of[b->lists ? size_t(it.op) : size_t(it.round) * 2 + it.op];
-        const uint32_t k = b->lists ? it.pos : next_in_group[gi]++;
         if (poisoned(b, it)) {          // ran on states a faulted round before it left out of step
             ++*n_stale;
             if (done)
@@ -980,22 +874,11 @@ static int64_t deliver_round(BRB_TransformBatcher *b, Round &R, BRB_TransformDon
             continue;
         }
         ++delivered;
-        int valid = 1;
-        const uint8_t *out;
-        if (b->zc) {
-            out = R.h_out + it.out_off;
-            if (b->algo == BRB_CRYPTO_FUNC_RC4_MD5 && it.op == BRB_CRYPTO_OP_READ)
-                valid = R.h_meta[R.group_valid[gi] + k];
-        } else if (b->algo == BRB_CRYPTO_FUNC_RC4) {
-            out = R.h_out + it.in_off;
-        } else if (it.op == BRB_CRYPTO_OP_WRITE) {
-            out = R.h_out + it.out_off;
-        } else {
-            out = R.h_in + it.in_off;
-            valid = R.h_meta[R.group_valid[gi] + k];
-        }
+        const Where &w = by_op[it.op];
+        const int64_t gi = R.plan.group_of[brb_plan::group_key(it, b->lists)];
+        const int valid = w.has_valid() ? R.h_meta[R.group_valid[gi] + it.pos] : 1;
         if (done)
-            done(user, it.conn, it.op, out, it.out_len, valid);
+            done(user, it.conn, it.op, w.result(it), it.out_len, valid);
     }
     if (*n_stale)
         set_err("%lld buffers of connections whose states a faulted round left out of step were dropped (re-key "
