@@ -173,6 +173,10 @@ _SIGNATURES = [
     ("BRB_RC4MD5_OpenListBatch", ctypes.c_int,
      [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
       ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint, ctypes.c_void_p]),
+    ("BRB_RC4_MixedListBatch", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
+      ctypes.c_void_p, ctypes.c_uint, ctypes.c_void_p]),
     ("BRB_Base64EncodeBatch", ctypes.c_int,
      [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p,
       ctypes.c_uint, ctypes.c_void_p]),
@@ -189,6 +193,12 @@ _SIGNATURES = [
     ("BRB_TransformBatcherCreate", ctypes.c_void_p, [ctypes.c_uint32, ctypes.c_uint64, ctypes.c_int]),
     ("BRB_TransformBatcherDestroy", None, [ctypes.c_void_p]),
     ("BRB_TransformBatcherEnable", ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_int]),
+    ("BRB_TransformBatcherEnableAlgo", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int, ctypes.c_void_p, ctypes.c_int]),
+    ("BRB_TransformBatcherEnableBatchAlgo", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+      ctypes.c_void_p]),
+    ("BRB_TransformBatcherDisable", ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32]),
     ("BRB_TransformBatcherRead", ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32]),
     ("BRB_TransformBatcherWrite", ctypes.c_int,
      [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64]),
@@ -931,6 +941,28 @@ def rc4md5_open_list_batch(states, frames, buf_offsets, buf_lengths, stream_firs
     return out, valid
 
 
+RC4_KIND_CRYPT, RC4_KIND_FRAME, RC4_KIND_OPEN = 0, 1, 2   # BRB_RC4_KIND_*
+
+
+def rc4_mixed_list_batch(states, stream_kind, data, buf_offsets, buf_lengths, out_offsets, stream_first_buf, out=None,
+                         salts=None, valid=None, state_index=None, stream=None, async_=False):
+    """BRB_RC4_MixedListBatch: stream i is of stream_kind[i] (RC4_KIND_*, uint8) and uses
+    states[state_index[i]] (uint32; None: states[i]); buffer k = data[buf_offsets[k]:+buf_lengths[k]] ->
+    out[out_offsets[k]:] (out None: data itself, for calls that work in place), 30 bytes longer for a FRAME
+    stream.  salts (uint64 per buffer) is read for FRAME buffers, valid (uint8 per buffer) written for OPEN
+    buffers; either may be None when no stream is of that kind.  Streams of one kind should be adjacent: a
+    wave of 64 streams runs every kind it holds, one after another.  Returns (out, valid)."""
+    out = data if out is None else out
+    _same_kind(data, states, stream_kind, out, buf_offsets, buf_lengths, out_offsets, stream_first_buf, salts, valid,
+               state_index)
+    flags, h = _mode(data, stream, async_)
+    _check(lib().BRB_RC4_MixedListBatch(_ptr(states), _nbytes(states) // RC4_STATE_BYTES, _ptr(state_index),
+                                        _ptr(stream_kind), _ptr(data), _ptr(out), _ptr(buf_offsets), _ptr(buf_lengths),
+                                        _ptr(out_offsets), _ptr(salts), _ptr(stream_first_buf),
+                                        len(stream_first_buf) - 1, _ptr(valid), flags, h), "BRB_RC4_MixedListBatch")
+    return out, valid
+
+
 # ---- MemBuffer Blowfish (SURVEY §8 f3) ------------------------------------------------------------
 def membuf_span(data_size: int) -> int:
     """BRB_MEMBUF_SPAN: bytes a call touches after buf + offset; data_size = size + offset to
@@ -1033,6 +1065,7 @@ BATCHER_ZERO_COPY = 0x100
 BATCHER_PIPELINED = 0x200    # BRB_BATCHER_PIPELINED: two arenas, flush_async()
 BATCHER_ALL_DEVICES = 0x400  # BRB_BATCHER_ALL_DEVICES: connections partitioned over the devices
 BATCHER_CONN_LISTS = 0x800   # BRB_BATCHER_CONN_LISTS: one launch per direction, a buffer list per connection
+BATCHER_MIXED = 0x1000       # BRB_BATCHER_MIXED: an algo per connection, one launch per round
 OP_READ, OP_WRITE = 0, 1
 TransformDone = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int, ctypes.c_void_p, ctypes.c_uint32,
                                  ctypes.c_int)
@@ -1074,10 +1107,13 @@ class TransformBatcher:
     region per arena, since a running round's buffers must stay unchanged until delivered.
 
     conn_lists=True creates it with BRB_BATCHER_CONN_LISTS: a round is one launch per direction, each
-    connection's buffers a list walked between one load and one store of its state."""
+    connection's buffers a list walked between one load and one store of its state.
+
+    mixed=True creates it with BRB_BATCHER_MIXED: `algo` is only the default, enable(conn, key, algo) gives
+    a connection its own, and a round is one launch whatever the connections' algos."""
 
     def __init__(self, max_conns: int, max_round_bytes: int, algo: int = CRYPTO_FUNC_RC4_MD5, zero_copy: bool = False,
-                 pipelined: bool = False, all_devices: bool = False, conn_lists: bool = False):
+                 pipelined: bool = False, all_devices: bool = False, conn_lists: bool = False, mixed: bool = False):
         self._L = lib()
         n_reg = 2 if pipelined else 1
         self._regions = [HostRegion(max(max_round_bytes, 1)) for _ in range(n_reg)] if zero_copy else None
@@ -1087,7 +1123,8 @@ class TransformBatcher:
                                                     algo | (BATCHER_ZERO_COPY if zero_copy else 0) |
                                                     (BATCHER_PIPELINED if pipelined else 0) |
                                                     (BATCHER_ALL_DEVICES if all_devices else 0) |
-                                                    (BATCHER_CONN_LISTS if conn_lists else 0))
+                                                    (BATCHER_CONN_LISTS if conn_lists else 0) |
+                                                    (BATCHER_MIXED if mixed else 0))
         if not self.h:
             raise RuntimeError("BRB_TransformBatcherCreate: " + self._L.BRB_CryptoGPU_LastError().decode())
 
@@ -1114,18 +1151,34 @@ class TransformBatcher:
     def __del__(self):
         self.close()
 
-    def enable(self, conn: int, key: bytes):
+    def enable(self, conn: int, key: bytes, algo: int | None = None):
+        """BRB_TransformBatcherEnable; with algo, BRB_TransformBatcherEnableAlgo (the connection's own algo)."""
+        if algo is not None:
+            _check(self._L.BRB_TransformBatcherEnableAlgo(self.h, conn, algo, bytes(key), len(key)),
+                   "BRB_TransformBatcherEnableAlgo")
+            return
         _check(self._L.BRB_TransformBatcherEnable(self.h, conn, bytes(key), len(key)), "BRB_TransformBatcherEnable")
 
-    def enable_batch(self, conns, keys):
+    def disable(self, conn: int):
+        """BRB_TransformBatcherDisable: both states zeroed, read / write refuse the connection until enable."""
+        _check(self._L.BRB_TransformBatcherDisable(self.h, conn), "BRB_TransformBatcherDisable")
+
+    def enable_batch(self, conns, keys, algos=None):
         """BRB_TransformBatcherEnableBatch: connection conns[i] gets keys[i] (bytes), read and write
-        state, in one GPU call."""
+        state, in one GPU call.  With algos (one per connection), BRB_TransformBatcherEnableBatchAlgo."""
         if len(conns) != len(keys):
             raise ValueError("conns and keys differ in length")
         ids = np.ascontiguousarray(conns, np.uint32)
         blob, offs, lens = pack_keys(keys)
         if blob.size == 0:
             blob = np.zeros(1, np.uint8)
+        if algos is not None:
+            if len(algos) != len(conns):
+                raise ValueError("conns and algos differ in length")
+            al = np.ascontiguousarray(algos, np.uint8)
+            _check(self._L.BRB_TransformBatcherEnableBatchAlgo(self.h, _ptr(ids), len(ids), _ptr(al), _ptr(blob), _ptr(offs),
+                                                               _ptr(lens)), "BRB_TransformBatcherEnableBatchAlgo")
+            return
         _check(self._L.BRB_TransformBatcherEnableBatch(self.h, _ptr(ids), len(ids), _ptr(blob), _ptr(offs), _ptr(lens)),
                "BRB_TransformBatcherEnableBatch")
 

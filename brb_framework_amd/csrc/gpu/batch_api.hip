@@ -1322,6 +1322,97 @@ int BRB_RC4MD5_OpenListBatch(BRB_RC4_State *states, const void *frames, void *ou
     });
 }
 
+// Streams of mixed kind (rc4_mixed_kernels.hip): stream i is of kind[i] and uses states[sidx ? sidx[i] : i].
+// Host mode: NamedCtx stages the named states densely, so the kernel runs without an index; the inputs'
+// span in, the outputs' span in both directions (one span when the call works in place), valid over the
+// named buffers in both directions, so the entries of buffers that are not OPEN keep the caller's bytes.
+int BRB_RC4_MixedListBatch(BRB_RC4_State *states, uint64_t n_states, const uint32_t *sidx, const uint8_t *kind,
+                           const void *in, void *out, const uint64_t *offsets, const uint32_t *lengths,
+                           const uint64_t *out_offsets, const uint64_t *salts, const uint64_t *first, uint64_t n,
+                           uint8_t *valid, unsigned flags, void *stream)
+{
+    t_err.clear();
+    if (n == 0)
+        return BRB_BATCH_OK;
+    if (!states || !kind || !in || !out || !offsets || !lengths || !out_offsets || !first) {
+        set_err("NULL states, stream_kind, in, out, buf_offsets, buf_lengths, out_offsets or stream_first_buf");
+        return BRB_BATCH_BADARG;
+    }
+    if (flags & BRB_BATCH_ALL_DEVICES) {
+        set_err("BRB_RC4_MixedListBatch does not split over devices: call it per device");
+        return BRB_BATCH_BADARG;
+    }
+    if (!items_ok(n) || !flags_ok(flags))
+        return BRB_BATCH_BADARG;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (flags & BRB_BATCH_DEVICE) {
+        if (int ok = device_ok(); ok != BRB_BATCH_OK)
+            return ok;
+        return device_run(brb::launch_rc4_mixed_list(bytes(states), kind, bytes(in), bytes(out), offsets, lengths, out_offsets,
+                                                     salts, first, n, valid, s, sidx),
+                          s, flags);
+    }
+    // host mode: every list is host memory and is checked before anything runs
+    bool any_frame = false, any_open = false;
+    for (uint64_t i = 0; i < n; i++) {
+        if (kind[i] > BRB_RC4_KIND_OPEN) {
+            set_err("stream %llu: kind %u (0 crypt, 1 frame, 2 open)", (unsigned long long)i, unsigned(kind[i]));
+            return BRB_BATCH_BADARG;
+        }
+        any_frame |= kind[i] == BRB_RC4_KIND_FRAME;
+        any_open |= kind[i] == BRB_RC4_KIND_OPEN;
+    }
+    if ((any_frame && !salts) || (any_open && !valid)) {
+        set_err(any_frame && !salts ? "NULL salts with a FRAME stream" : "NULL valid with an OPEN stream");
+        return BRB_BATCH_BADARG;
+    }
+    const BufList bl = buf_list(first, n);
+    if (!bl.ok)
+        return BRB_BATCH_BADARG;
+    NamedCtx named{bytes(states), sidx, n, sizeof(BRB_RC4_State), {}};
+    if (!named.ok(n_states, "a connection's buffers of one call go in its stream's list"))
+        return BRB_BATCH_BADARG;
+    std::vector<uint64_t> olen(bl.count);   // bytes written per buffer
+    for (uint64_t i = 0; i < n; i++)
+        for (uint64_t k = bl.first[i]; k < bl.first[i + 1]; k++)
+            olen[k] = uint64_t(lengths[bl.k0 + k]) + (kind[i] == BRB_RC4_KIND_FRAME ? BRB_RC4MD5_HEADER : 0);
+    Span sp = span_rebase(offsets + bl.k0, lengths + bl.k0, bl.count);
+    if (!sp.ok)
+        return BRB_BATCH_BADARG;
+    Span so = span_rebase(out_offsets + bl.k0, olen.data(), bl.count);
+    if (!so.ok)
+        return BRB_BATCH_BADARG;
+    if (int ok = device_ok(); ok != BRB_BATCH_OK)
+        return ok;
+    const bool same = in == out;
+    if (same && sp.bytes() && so.bytes()) {   // in place: one span, staged in both directions
+        const uint64_t lo = std::min(sp.lo, so.lo), hi = std::max(sp.hi, so.hi);
+        for (uint64_t k = 0; k < bl.count; k++) {
+            sp.off[k] += lengths[bl.k0 + k] ? sp.lo - lo : 0;
+            so.off[k] += olen[k] ? so.lo - lo : 0;
+        }
+        sp.lo = so.lo = lo;
+        sp.hi = so.hi = hi;
+    }
+    Staging st;
+    const size_t i_st = st.inout(named.gather(), sizeof(BRB_RC4_State) * n);
+    const size_t i_out = st.inout(bytes(out) + so.lo, so.bytes());
+    const size_t i_in = same && sp.bytes() && so.bytes() ? i_out : st.in(bytes(in) + sp.lo, sp.bytes());
+    const size_t i_off = st.in(sp.off.data(), 8 * bl.count);
+    const size_t i_ooff = st.in(so.off.data(), 8 * bl.count);
+    const size_t i_len = st.in(lengths + bl.k0, 4 * bl.count);
+    const size_t i_salt = any_frame ? st.in(salts + bl.k0, 8 * bl.count) : 0;
+    const size_t i_first = st.in(bl.first.data(), 8 * (n + 1));
+    const size_t i_kind = st.in(kind, n);
+    const size_t i_val = any_open ? st.inout(valid + bl.k0, bl.count) : 0;
+    return named.scatter(st.run(s, nullptr, [&] {
+        return launched(brb::launch_rc4_mixed_list(st.dev(i_st), st.dev(i_kind), st.dev(i_in), st.dev(i_out),
+                                                   st.dev<uint64_t>(i_off), st.dev<uint32_t>(i_len), st.dev<uint64_t>(i_ooff),
+                                                   any_frame ? st.dev<uint64_t>(i_salt) : nullptr, st.dev<uint64_t>(i_first), n,
+                                                   any_open ? st.dev(i_val) : nullptr, s));
+    }));
+}
+
 int BRB_MD5BatchSegments(const void *data, const uint64_t *soff, const uint32_t *slen, const uint64_t *first, uint64_t n_rec,
                          unsigned char (*digests)[16], unsigned flags, void *stream)
 {

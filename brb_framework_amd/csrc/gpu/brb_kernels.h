@@ -116,6 +116,14 @@ hipError_t launch_rc4md5_frame_list(uint8_t *states, const uint8_t *payload, con
 hipError_t launch_rc4md5_open_list(uint8_t *states, const uint8_t *in, uint8_t *out, const uint64_t *offs,
                                    const uint32_t *lens, const uint64_t *first, uint64_t n, uint8_t *valid,
                                    hipStream_t s, const uint32_t *sidx = nullptr, const uint64_t *ooffs = nullptr);
+// Streams of mixed kind in one launch (rc4_mixed_kernels.hip): stream i is walked as the list launcher of
+// kind[i] (BRB_RC4_KIND_*) walks it.  Every buffer has its input offset offs[k] in `in` and its output
+// offset ooffs[k] in `out`; salts is read for FRAME buffers only, valid written for OPEN buffers only
+// (either may be nullptr when no stream is of that kind).  Lone waves: no pair fault word.
+hipError_t launch_rc4_mixed_list(uint8_t *states, const uint8_t *kind, const uint8_t *in, uint8_t *out,
+                                 const uint64_t *offs, const uint32_t *lens, const uint64_t *ooffs, const uint64_t *salts,
+                                 const uint64_t *first, uint64_t n, uint8_t *valid, hipStream_t s,
+                                 const uint32_t *sidx = nullptr);
 
 // Key setup (keysetup_kernels.hip): key i = keys[koffs[i] .. + klens[i]).
 // RC4: the zeroed-then-BRB_RC4_Init state of key i is written (all 264 bytes) to states[slots ? slots[i] : i],

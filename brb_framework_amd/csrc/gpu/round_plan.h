@@ -9,6 +9,11 @@
 // buffers a stream of its own; with them it is one direction, its streams in order of first
 // appearance and stream i's buffers first[i] .. first[i + 1] - 1 in submission order.  Groups come in
 // key order -- 2 * sub-round + op, with lists op -- so READ before WRITE; empty ones are skipped.
+//
+// The mixed layout (plan_round_mixed, BRB_BATCHER_MIXED) is one group for the whole round: every
+// (direction, connection) is a stream of the mixed kernel, with its kind in kind u8[streams] behind
+// first.  Streams are sorted by kind (a wave whose lanes agree runs one body), inside a kind in order
+// of first appearance; stream i's buffers are first[i] .. first[i + 1] - 1 in submission order.
 #pragma once
 
 #include <cstddef>
@@ -30,6 +35,7 @@ struct Item {
     uint32_t round;   // sub-round: the buffer's rank among its connection's buffers in its direction
     uint32_t epoch;   // the connection's key epoch at submission (BRB_TransformBatcher::epoch)
     uint32_t pos;     // the buffer's index in its group
+    uint8_t algo;     // the connection's algo at submission (1 RC4, 2 RC4_MD5); read by the mixed layout only
 };
 
 struct Group {
@@ -37,6 +43,7 @@ struct Group {
     uint32_t count;     // buffers
     uint32_t streams;   // entries of sidx (without connection lists: count)
     size_t o_sidx, o_first, o_offs, o_lens, o_ooffs, o_salts;   // o_first: connection lists only
+    size_t o_kind = 0;                                          // the mixed layout only
 };
 
 struct Plan {
@@ -140,6 +147,78 @@ inline bool plan_round(std::vector<Item> &items, uint32_t max_conns, bool lists,
     for (const Group &g : p->groups)
         if (lists)
             meta_at<uint64_t>(meta, g.o_first)[g.streams] = g.count;
+    return true;
+}
+
+// ---- the mixed layout ---------------------------------------------------------------------------
+// Stream kinds, the values of BRB_RC4_KIND_* (brb_crypto.h is not included here).
+constexpr uint8_t kKindCrypt = 0, kKindFrame = 1, kKindOpen = 2;
+
+// An RC4 connection crypts either way; an RC4_MD5 connection opens what it reads and frames what it writes.
+inline uint8_t item_kind(const Item &it) { return it.algo != 2 ? kKindCrypt : it.op == 1 ? kKindFrame : kKindOpen; }
+
+// plan_round for a round that is one launch of the mixed kernel: p->groups holds one group (none for
+// an empty round) and group_of is {0}.  A stream's kind is that of its first buffer.  Sets every
+// item's round and pos (its index among the round's buffers, also its valid flag's).  Returns false,
+// with nothing written to meta, when the metadata and a valid flag per item do not fit in cap bytes.
+inline bool plan_round_mixed(std::vector<Item> &items, uint32_t max_conns, bool zc, uint64_t zc_base, uint8_t *meta,
+                             size_t cap, Plan *p)
+{
+    // rank per (direction, connection); `seen` ends as every stream's buffer count
+    std::vector<uint32_t> seen(size_t(2) * max_conns, 0);
+    std::vector<uint8_t> kind_of(size_t(2) * max_conns, 0);
+    uint32_t n_streams[3] = {0, 0, 0}, n_bufs[3] = {0, 0, 0};
+    for (Item &it : items) {
+        const size_t c = size_t(it.op) * max_conns + it.conn;
+        it.round = seen[c]++;
+        if (it.round == 0)
+            ++n_streams[kind_of[c] = item_kind(it)];
+        ++n_bufs[kind_of[c]];
+    }
+    Cursor cur{cap};
+    p->groups.clear();
+    p->group_of.assign(1, -1);
+    Group g;
+    g.op = 0;
+    g.count = n_bufs[0] + n_bufs[1] + n_bufs[2];
+    g.streams = n_streams[0] + n_streams[1] + n_streams[2];
+    if (g.count) {
+        g.o_sidx = cur.take(g.streams, 4);
+        g.o_first = cur.take(size_t(g.streams) + 1, 8);
+        g.o_kind = cur.take(g.streams, 1);
+        g.o_offs = cur.take(g.count, 8);
+        g.o_lens = cur.take(g.count, 4);
+        g.o_ooffs = cur.take(g.count, 8);
+        g.o_salts = cur.take(g.count, 8);
+        p->group_of[0] = 0;
+        p->groups.push_back(g);
+    }
+    p->o_valid = cur.at;
+    if (!cur.fits || cur.at > cap || items.size() > cap - cur.at)
+        return false;
+    // fill: the next free stream and buffer index of every kind; an item that opens a stream takes the
+    // stream's range of buffers, and `seen` turns into the stream's next free index
+    uint32_t s_at[3] = {0, n_streams[0], n_streams[0] + n_streams[1]}, b_at[3] = {0, n_bufs[0], n_bufs[0] + n_bufs[1]};
+    for (Item &it : items) {
+        const size_t c = size_t(it.op) * max_conns + it.conn;
+        if (it.round == 0) {
+            const uint8_t kd = kind_of[c];
+            const uint32_t s = s_at[kd]++;
+            meta_at<uint32_t>(meta, g.o_sidx)[s] = uint32_t(c);
+            meta_at<uint64_t>(meta, g.o_first)[s] = b_at[kd];
+            meta_at<uint8_t>(meta, g.o_kind)[s] = kd;
+            const uint32_t bufs = seen[c];
+            seen[c] = b_at[kd];
+            b_at[kd] += bufs;
+        }
+        const uint32_t k = it.pos = seen[c]++;
+        meta_at<uint64_t>(meta, g.o_offs)[k] = zc ? it.in_off - zc_base : it.in_off;
+        meta_at<uint32_t>(meta, g.o_lens)[k] = it.in_len;
+        meta_at<uint64_t>(meta, g.o_ooffs)[k] = it.out_off;
+        meta_at<uint64_t>(meta, g.o_salts)[k] = it.salt;
+    }
+    if (g.count)
+        meta_at<uint64_t>(meta, g.o_first)[g.streams] = g.count;
     return true;
 }
 

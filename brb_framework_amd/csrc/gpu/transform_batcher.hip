@@ -15,6 +15,11 @@
 // the list kernels (rc4_list_kernels.hip), its buffers in submission order, so the round is one
 // launch per direction -- READ, then WRITE -- and a state is loaded and stored once per round.
 //
+// Mixed rounds (BRB_BATCHER_MIXED): every connection has an algo of its own, as the reference's
+// crypto->algo_code (ev_kq_aio_transform.c:75-108), and the round is one launch of the mixed kernel
+// (rc4_mixed_kernels.hip), every (direction, connection) a stream of the kind its algo and direction
+// give, streams sorted by kind.  Every kind reads the input arena and writes the output arena.
+//
 // Both are one plan (round_plan.h: a round's launches and the metadata each reads, host arithmetic
 // only) and one launch table (where(), launch_groups()); a sub-round group is a list group whose
 // streams hold one buffer each.
@@ -215,6 +220,7 @@ struct BRB_TransformBatcher {
     int algo = 0;
     bool zc = false;           // zero-copy rounds
     bool lists = false;        // BRB_BATCHER_CONN_LISTS: one launch per direction, a buffer list per connection
+    bool mixed = false;        // BRB_BATCHER_MIXED: an algo per connection, one launch per round (implies lists)
     int n_rounds = 1;          // 2 when pipelined
     int cur = 0;               // the round Read/Write fill
     int dev = 0;
@@ -231,6 +237,7 @@ struct BRB_TransformBatcher {
     uint64_t max_items = 0;    // buffers per round: 4 per connection on average
     Round r[2];
     std::vector<uint8_t> enabled;
+    std::vector<uint8_t> conn_algo;        // the algo a connection was enabled with (`algo` unless mixed)
     // Key epochs: Enable starts a connection's next epoch; a round dropped for a device
     // fault leaves the states of its connections out of step, so their epoch is poisoned
     // (poison_upto[c] = the last poisoned epoch).  A buffer of a poisoned epoch is never delivered as
@@ -293,9 +300,10 @@ struct BRB_TransformBatcher {
 // What a successful key setup leaves behind (Enable and EnableBatch): the connection takes buffers
 // again and starts its next key epoch, so buffers from here on belong to the fresh key and a
 // poisoned connection is re-keyed.
-static void key_installed(BRB_TransformBatcher *b, uint32_t conn)
+static void key_installed(BRB_TransformBatcher *b, uint32_t conn, int algo)
 {
     b->enabled[conn] = 1;
+    b->conn_algo[conn] = uint8_t(algo);
     __atomic_fetch_add(&b->epoch[conn], 1u, __ATOMIC_RELEASE);   // buffers from here on: the fresh key
 }
 
@@ -336,8 +344,9 @@ BRB_TransformBatcher *BRB_TransformBatcherCreate(uint32_t max_conns, uint64_t ma
     }
     const bool zc = (algo & BRB_BATCHER_ZERO_COPY) != 0;
     const bool pipelined = (algo & BRB_BATCHER_PIPELINED) != 0;
-    const bool lists = (algo & BRB_BATCHER_CONN_LISTS) != 0;
-    algo &= ~(BRB_BATCHER_ZERO_COPY | BRB_BATCHER_PIPELINED | BRB_BATCHER_CONN_LISTS);
+    const bool mixed = (algo & BRB_BATCHER_MIXED) != 0;
+    const bool lists = mixed || (algo & BRB_BATCHER_CONN_LISTS) != 0;
+    algo &= ~(BRB_BATCHER_ZERO_COPY | BRB_BATCHER_PIPELINED | BRB_BATCHER_CONN_LISTS | BRB_BATCHER_MIXED);
     if (max_conns == 0 || max_round_bytes == 0 || (algo != BRB_CRYPTO_FUNC_RC4 && algo != BRB_CRYPTO_FUNC_RC4_MD5)) {
         set_err("max_conns and max_round_bytes must be > 0 and algo RC4 (1) or RC4_MD5 (2)");
         return nullptr;
@@ -354,8 +363,10 @@ BRB_TransformBatcher *BRB_TransformBatcherCreate(uint32_t max_conns, uint64_t ma
     b->algo = algo;
     b->zc = zc;
     b->lists = lists;
+    b->mixed = mixed;
     b->n_rounds = pipelined ? 2 : 1;
     b->enabled.assign(max_conns, 0);
+    b->conn_algo.assign(max_conns, uint8_t(algo));
     b->epoch.assign(max_conns, 0);
     b->poison_upto.assign(max_conns, 0);
     // outputs: every buffer may grow by a frame header; metadata: per item and sub-round arrays
@@ -395,15 +406,11 @@ void BRB_TransformBatcherDestroy(BRB_TransformBatcher *b)
     delete b;
 }
 
-int BRB_TransformBatcherEnable(BRB_TransformBatcher *b, uint32_t conn, const void *key, int key_sz)
+}  // extern "C"
+
+// Enable and EnableAlgo on a batcher that is not an all-devices router; algo is the connection's from here on.
+static int enable_one(BRB_TransformBatcher *b, uint32_t conn, int algo, const void *key, int key_sz)
 {
-    brb_api::clear_err();
-    if (!b || !key || key_sz <= 0 || conn >= b->max_conns) {
-        set_err("bad batcher, key or connection id");
-        return BRB_BATCH_BADARG;
-    }
-    if (!b->subs.empty())
-        return BRB_TransformBatcherEnable(b->subs[conn % b->subs.size()], conn / uint32_t(b->subs.size()), key, key_sz);
     BRB_RC4_State st;
     memset(&st, 0, sizeof(st));              // ev_kq_aio_transform.c:78 memset of the crypto states
     BRB_RC4_Init(&st, static_cast<const unsigned char *>(key), key_sz);
@@ -416,7 +423,87 @@ int BRB_TransformBatcherEnable(BRB_TransformBatcher *b, uint32_t conn, const voi
             return fail_hip("hipMemcpyAsync H2D", e);
     if ((e = hipStreamSynchronize(b->stream)) != hipSuccess)
         return fail_hip("hipStreamSynchronize", e);
-    key_installed(b, conn);
+    key_installed(b, conn, algo);
+    return BRB_BATCH_OK;
+}
+
+// True (and the reason set) when the filling round holds a buffer of a connection for which want(conn)
+// holds: EnableAlgo, EnableBatchAlgo and Disable then change nothing, since the buffer would run under
+// another key, another algo or a zeroed state.  A scan of the round's slots; it must not overlap Read / Write.
+template <class Want>
+static bool round_holds(BRB_TransformBatcher *b, Want want)
+{
+    const Round &R = b->r[b->cur];
+    const uint64_t n = std::min<uint64_t>(R.n_slots, b->max_items);
+    for (uint64_t i = 0; i < n; i++)
+        if (R.slots[i].conn != kHole && want(R.slots[i].conn)) {
+            set_err("connection %u has a buffer in the round being filled: flush first", R.slots[i].conn);
+            return true;
+        }
+    return false;
+}
+
+extern "C" {
+
+int BRB_TransformBatcherEnable(BRB_TransformBatcher *b, uint32_t conn, const void *key, int key_sz)
+{
+    brb_api::clear_err();
+    if (!b || !key || key_sz <= 0 || conn >= b->max_conns) {
+        set_err("bad batcher, key or connection id");
+        return BRB_BATCH_BADARG;
+    }
+    if (!b->subs.empty())
+        return BRB_TransformBatcherEnable(b->subs[conn % b->subs.size()], conn / uint32_t(b->subs.size()), key, key_sz);
+    // a mixed batcher: back to the default algo only with none of the connection's buffers waiting (their
+    // output sizes were taken under the algo they were submitted with)
+    if (b->mixed && b->conn_algo[conn] != b->algo && round_holds(b, [conn](uint32_t c) { return c == conn; }))
+        return BRB_BATCH_NOT_DONE;
+    return enable_one(b, conn, b->algo, key, key_sz);
+}
+
+int BRB_TransformBatcherEnableAlgo(BRB_TransformBatcher *b, uint32_t conn, int algo, const void *key, int key_sz)
+{
+    brb_api::clear_err();
+    if (!b || !key || key_sz <= 0 || conn >= b->max_conns) {
+        set_err("bad batcher, key or connection id");
+        return BRB_BATCH_BADARG;
+    }
+    if (algo != BRB_CRYPTO_FUNC_RC4 && algo != BRB_CRYPTO_FUNC_RC4_MD5) {
+        set_err("algo %d: RC4 (1) or RC4_MD5 (2)", algo);
+        return BRB_BATCH_BADARG;
+    }
+    if (!b->subs.empty())
+        return BRB_TransformBatcherEnableAlgo(b->subs[conn % b->subs.size()], conn / uint32_t(b->subs.size()), algo, key,
+                                              key_sz);
+    if (!b->mixed && algo != b->algo) {
+        set_err("algo %d on a batcher created for algo %d without BRB_BATCHER_MIXED", algo, b->algo);
+        return BRB_BATCH_BADARG;
+    }
+    if (round_holds(b, [conn](uint32_t c) { return c == conn; }))
+        return BRB_BATCH_NOT_DONE;
+    return enable_one(b, conn, algo, key, key_sz);
+}
+
+int BRB_TransformBatcherDisable(BRB_TransformBatcher *b, uint32_t conn)
+{
+    brb_api::clear_err();
+    if (!b || conn >= b->max_conns) {
+        set_err("bad batcher or connection id");
+        return BRB_BATCH_BADARG;
+    }
+    if (!b->subs.empty())
+        return BRB_TransformBatcherDisable(b->subs[conn % b->subs.size()], conn / uint32_t(b->subs.size()));
+    if (round_holds(b, [conn](uint32_t c) { return c == conn; }))
+        return BRB_BATCH_NOT_DONE;
+    DeviceGuard g(b->dev);
+    hipError_t e;
+    if ((e = g.error()) != hipSuccess)
+        return fail_hip("hipSetDevice", e);
+    // on the batcher's stream: behind the kernels of a round FlushAsync left running, ahead of GetState
+    for (int op = 0; op < 2; op++)
+        if ((e = hipMemsetAsync(b->state(conn, op), 0, sizeof(BRB_RC4_State), b->stream)) != hipSuccess)
+            return fail_hip("hipMemsetAsync", e);
+    b->enabled[conn] = 0;   // ev_kq_aio_transform.c:110-123: Read / Write refuse it as one never enabled
     return BRB_BATCH_OK;
 }
 
@@ -436,7 +523,8 @@ static int submit(BRB_TransformBatcher *b, uint32_t conn, int op, const void *da
         return BRB_BATCH_BADARG;
     }
     Round &R = b->r[b->cur];
-    const uint32_t out_len = len + (b->algo == BRB_CRYPTO_FUNC_RC4_MD5 && op == BRB_CRYPTO_OP_WRITE ? kHdr : 0);
+    const int algo = b->conn_algo[conn];   // the connection's at submission; `b->algo` unless mixed
+    const uint32_t out_len = len + (algo == BRB_CRYPTO_FUNC_RC4_MD5 && op == BRB_CRYPTO_OP_WRITE ? kHdr : 0);
     // Slot order is delivery order.  A thread's slots and bytes come from its own chunks, taken in
     // increasing order, so the buffers of a connection (owned by one thread) keep their order.
     // Slots of a chunk left unused stay holes; the metadata arrays fit max_items slots.
@@ -476,7 +564,7 @@ static int submit(BRB_TransformBatcher *b, uint32_t conn, int op, const void *da
     }
     Item &it = R.slots[k.slot];
     const uint64_t in_off = k.in, out_off = k.out;
-    it = Item{conn, op, in_off, len, out_off, out_len, salt, 0, ep};
+    it = Item{conn, op, in_off, len, out_off, out_len, salt, 0, ep, 0, uint8_t(algo)};
     if (b->zc) {
         uintptr_t d = 0;
         if (len && !host_to_device(data, len, &d, b->dev)) {
@@ -519,6 +607,7 @@ struct EnablePart {
     BRB_TransformBatcher *b = nullptr;
     std::vector<uint32_t> conns;       // the part's own connection ids
     std::vector<uint64_t> which;       // index into the caller's arrays
+    std::vector<uint8_t> algos;        // the algo every connection takes
     std::vector<uint8_t> host;         // keys | offsets | lengths | slots (kept until the stream has drained)
     uint8_t *dev = nullptr;
     bool enqueued = false;
@@ -582,19 +671,20 @@ struct EnablePart {
                 (void)hipFree(dev);     // the stream has drained (or failed): nothing reads it any more
         }
         const bool ok = err.empty();
-        for (uint32_t c : conns)
+        for (size_t k = 0; k < conns.size(); k++)
             if (ok)
-                key_installed(b, c);
+                key_installed(b, conns[k], algos[k]);
             else
-                b->enabled[c] = 0;      // its states may be half written: refused until enabled again
+                b->enabled[conns[k]] = 0;   // its states may be half written: refused until enabled again
         return ok;
     }
 };
 
 }  // namespace
 
-extern "C" int BRB_TransformBatcherEnableBatch(BRB_TransformBatcher *b, const uint32_t *conns, uint64_t n, const void *keys,
-                                               const uint64_t *key_offsets, const uint32_t *key_lengths)
+// EnableBatch (algos == nullptr, !check_pending: every connection takes its batcher's algo) and EnableBatchAlgo.
+static int enable_batch(BRB_TransformBatcher *b, const uint32_t *conns, uint64_t n, const uint8_t *algos, const void *keys,
+                        const uint64_t *key_offsets, const uint32_t *key_lengths, bool check_pending)
 {
     brb_api::clear_err();
     if (!b) {
@@ -607,8 +697,16 @@ extern "C" int BRB_TransformBatcherEnableBatch(BRB_TransformBatcher *b, const ui
         set_err("NULL conns, keys, key_offsets or key_lengths");
         return BRB_BATCH_BADARG;
     }
+    const uint32_t G = b->subs.empty() ? 1u : uint32_t(b->subs.size());
+    std::vector<EnablePart> parts(G);
+    for (uint32_t g = 0; g < G; g++)
+        parts[g].b = b->subs.empty() ? b : b->subs[g];
     std::vector<uint8_t> listed(b->max_conns, 0);
     for (uint64_t i = 0; i < n; i++) {
+        if (algos && algos[i] != BRB_CRYPTO_FUNC_RC4 && algos[i] != BRB_CRYPTO_FUNC_RC4_MD5) {
+            set_err("entry %llu: algo %u: RC4 (1) or RC4_MD5 (2)", (unsigned long long)i, unsigned(algos[i]));
+            return BRB_BATCH_BADARG;
+        }
         if (conns[i] >= b->max_conns || key_lengths[i] == 0 || listed[conns[i]]) {
             set_err("entry %llu: connection %u %s", (unsigned long long)i, conns[i],
                     conns[i] >= b->max_conns ? "is out of range" : key_lengths[i] == 0 ? "has a zero key length"
@@ -619,16 +717,28 @@ extern "C" int BRB_TransformBatcherEnableBatch(BRB_TransformBatcher *b, const ui
             set_err("entry %llu: key offset + length wraps", (unsigned long long)i);
             return BRB_BATCH_BADARG;
         }
+        const BRB_TransformBatcher *pb = parts[conns[i] % G].b;
+        if (algos && !pb->mixed && algos[i] != pb->algo) {
+            set_err("entry %llu: algo %u on a batcher created for algo %d without BRB_BATCHER_MIXED", (unsigned long long)i,
+                    unsigned(algos[i]), pb->algo);
+            return BRB_BATCH_BADARG;
+        }
         listed[conns[i]] = 1;
     }
-    const uint32_t G = b->subs.empty() ? 1u : uint32_t(b->subs.size());
-    std::vector<EnablePart> parts(G);
-    for (uint32_t g = 0; g < G; g++)
-        parts[g].b = b->subs.empty() ? b : b->subs[g];
+    // part g's connection c is the caller's c * G + g.  EnableBatch keeps its rule (no check) but for a
+    // connection of a mixed batcher whose algo it changes back to the default, as Enable
+    for (uint32_t g = 0; g < G; g++) {
+        BRB_TransformBatcher *pb = parts[g].b;
+        if ((check_pending || pb->mixed) && round_holds(pb, [&](uint32_t c) {
+                return listed[size_t(c) * G + g] != 0 && (check_pending || pb->conn_algo[c] != pb->algo);
+            }))
+            return BRB_BATCH_NOT_DONE;
+    }
     for (uint64_t i = 0; i < n; i++) {
         EnablePart &p = parts[conns[i] % G];
         p.conns.push_back(conns[i] / G);
         p.which.push_back(i);
+        p.algos.push_back(algos ? algos[i] : uint8_t(p.b->algo));
     }
     for (EnablePart &p : parts)
         if (!p.conns.empty())
@@ -647,6 +757,19 @@ extern "C" int BRB_TransformBatcherEnableBatch(BRB_TransformBatcher *b, const ui
     set_err("EnableBatch: %u of %u parts failed, their listed connections are left disabled (%s)", failed, G,
             why.c_str());
     return BRB_BATCH_NOT_DONE;
+}
+
+extern "C" int BRB_TransformBatcherEnableBatch(BRB_TransformBatcher *b, const uint32_t *conns, uint64_t n, const void *keys,
+                                               const uint64_t *key_offsets, const uint32_t *key_lengths)
+{
+    return enable_batch(b, conns, n, nullptr, keys, key_offsets, key_lengths, false);
+}
+
+extern "C" int BRB_TransformBatcherEnableBatchAlgo(BRB_TransformBatcher *b, const uint32_t *conns, uint64_t n,
+                                                   const uint8_t *algos, const void *keys, const uint64_t *key_offsets,
+                                                   const uint32_t *key_lengths)
+{
+    return enable_batch(b, conns, n, algos, keys, key_offsets, key_lengths, true);
 }
 
 // A buffer of a poisoned key epoch (its connection's states went out of step in a dropped round).
@@ -685,7 +808,11 @@ struct Where {
     uint8_t *in, *out, *valid;   // device bases of the inputs, the outputs and the valid flags
     const uint8_t *h_out;        // the host's view of `out` (copy mode: once the D2H copies have landed)
     bool at_out_off;             // outputs lie at Item::out_off (the kernel takes ooffs), else they mirror in_off
-    bool has_valid() const { return kind == OPEN; }
+    bool mixed;                  // the kind is the buffer's own (its connection's algo at submission)
+    bool has_valid(const Item &it) const
+    {
+        return mixed ? it.algo == BRB_CRYPTO_FUNC_RC4_MD5 && it.op == BRB_CRYPTO_OP_READ : kind == OPEN;
+    }
     const uint8_t *result(const Item &it) const { return h_out + (at_out_off ? it.out_off : it.in_off); }
 };
 
@@ -693,6 +820,7 @@ static Where where(const BRB_TransformBatcher *b, const Round &R, int op)
 {
     Where w;
     w.kind = b->algo == BRB_CRYPTO_FUNC_RC4 ? Where::CRYPT : op == BRB_CRYPTO_OP_WRITE ? Where::FRAME : Where::OPEN;
+    w.mixed = b->mixed;
     if (b->zc) {
         // inputs read in place over PCIe (offs are relative to out_dev), outputs written into the
         // page-locked output arena
@@ -701,12 +829,14 @@ static Where where(const BRB_TransformBatcher *b, const Round &R, int op)
         w.h_out = R.h_out;
     } else {
         // an open decrypts in place in the input arena, which is copied back with the frames in it
+        // (a mixed round: every kind writes the output arena, so nothing comes back in the input arena)
+        const bool in_place = !b->mixed && w.kind == Where::OPEN;
         w.in = R.d_in;
-        w.out = w.kind == Where::OPEN ? R.d_in : R.d_out;
+        w.out = in_place ? R.d_in : R.d_out;
         w.valid = R.d_meta;
-        w.h_out = w.kind == Where::OPEN ? R.h_in : R.h_out;
+        w.h_out = in_place ? R.h_in : R.h_out;
     }
-    w.at_out_off = b->zc || w.kind == Where::FRAME;
+    w.at_out_off = b->zc || b->mixed || w.kind == Where::FRAME;
     return w;
 }
 
@@ -738,6 +868,15 @@ static int launch_groups(BRB_TransformBatcher *b, Round &R, size_t *vpos)
         if (int64_t(gi) == b->fault_launch)
             return fail_hip("kernel launch (injected fault)", hipErrorLaunchFailure);
         hipError_t e;
+        if (b->mixed) {   // the round's one group: a valid flag per buffer, written for the open buffers
+            R.group_valid[gi] = *vpos;
+            e = brb::launch_rc4_mixed_list(b->d_states, R.d_meta + g.o_kind, w.in, w.out, offs, lens, ooffs, salts, first,
+                                           g.streams, w.valid + *vpos, s, sidx);
+            *vpos += g.count;
+            if (e != hipSuccess)
+                return fail_hip("kernel launch", e);
+            continue;
+        }
         switch (w.kind) {
         case Where::CRYPT:
             e = b->lists ? brb::launch_rc4_crypt_list(b->d_states, w.in, w.out, offs, lens, first, g.streams, s, sidx, oo)
@@ -768,7 +907,9 @@ static int enqueue_round(BRB_TransformBatcher *b, Round &R, bool *started)
 {
     hipError_t e;
     // zero-copy: kernels address input buffers as out_dev + (device address - out_dev)
-    if (!brb_plan::plan_round(R.items, b->max_conns, b->lists, b->zc, uint64_t(R.out_dev), R.h_meta, b->meta_cap, &R.plan)) {
+    if (!(b->mixed ? brb_plan::plan_round_mixed(R.items, b->max_conns, b->zc, uint64_t(R.out_dev), R.h_meta, b->meta_cap, &R.plan)
+                   : brb_plan::plan_round(R.items, b->max_conns, b->lists, b->zc, uint64_t(R.out_dev), R.h_meta, b->meta_cap,
+                                          &R.plan))) {
         set_err("metadata overflow");
         return BRB_BATCH_NOT_DONE;
     }
@@ -793,7 +934,7 @@ static int enqueue_round(BRB_TransformBatcher *b, Round &R, bool *started)
     if (split && ((e = hipEventRecord(R.ev_kern, s)) != hipSuccess || (e = hipStreamWaitEvent(sd, R.ev_kern, 0)) != hipSuccess))
         return fail_hip("kernel event", e);
     if (!b->zc && ((e = hipMemcpyAsync(R.h_out, R.d_out, out_used, hipMemcpyDeviceToHost, sd)) != hipSuccess ||
-                   (b->algo == BRB_CRYPTO_FUNC_RC4_MD5 &&
+                   (b->algo == BRB_CRYPTO_FUNC_RC4_MD5 && !b->mixed &&
                     (e = hipMemcpyAsync(R.h_in, R.d_in, in_used, hipMemcpyDeviceToHost, sd)) != hipSuccess) ||
                    (vpos > o_valid && (e = hipMemcpyAsync(R.h_meta + o_valid, R.d_meta + o_valid, vpos - o_valid,
                                                           hipMemcpyDeviceToHost, sd)) != hipSuccess)))
@@ -875,8 +1016,8 @@ static int64_t deliver_round(BRB_TransformBatcher *b, Round &R, BRB_TransformDon
         }
         ++delivered;
         const Where &w = by_op[it.op];
-        const int64_t gi = R.plan.group_of[brb_plan::group_key(it, b->lists)];
-        const int valid = w.has_valid() ? R.h_meta[R.group_valid[gi] + it.pos] : 1;
+        const int64_t gi = b->mixed ? 0 : R.plan.group_of[brb_plan::group_key(it, b->lists)];
+        const int valid = w.has_valid(it) ? R.h_meta[R.group_valid[gi] + it.pos] : 1;
         if (done)
             done(user, it.conn, it.op, w.result(it), it.out_len, valid);
     }

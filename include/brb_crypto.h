@@ -574,6 +574,51 @@ int BRB_RC4MD5_OpenListBatch(BRB_RC4_State *states, const void *frames, void *ou
                              const uint32_t *buf_lengths, const uint64_t *stream_first_buf, uint64_t n_streams,
                              uint8_t *valid, unsigned flags, void *hip_stream);
 
+/* ---- Streams of mixed kind in one call ---------------------------------------------------------
+ * The reference fixes a connection's transform when it is enabled (EvAIOReqTransform_CryptoEnable
+ * stores crypto->algo_code per connection, ev_kq_aio_transform.c:75-108), so a daemon holds RC4 and
+ * RC4_MD5 connections side by side, and an RC4_MD5 connection opens in one direction and frames in
+ * the other.  The three list calls above take one kind per launch.  Here stream i carries its kind
+ * in stream_kind[i] and uses states[state_index ? state_index[i] : i] (n_states states; every stream
+ * of a call names a state of its own).  Stream i owns buffers stream_first_buf[i] ..
+ * stream_first_buf[i + 1] - 1; buffer k is in[buf_offsets[k] .. + buf_lengths[k]) and its result is
+ * written at out + out_offsets[k]: buf_lengths[k] bytes for CRYPT and OPEN, 30 + buf_lengths[k] for
+ * FRAME.  salts[k] is read for FRAME buffers only and valid[k] written for OPEN buffers only; salts may
+ * be NULL when no stream is FRAME, valid when none is OPEN.
+ * The result -- outputs, valid of OPEN buffers, all 264 bytes of every named state -- is exactly
+ * what the scalar calls leave when applied to the stream's buffers in list order, as the list call of
+ * the stream's kind defines it.  States not named keep every byte, and so do valid entries of
+ * buffers that are not OPEN.  A stream without buffers keeps its state bit for bit; an empty buffer
+ * reads and writes nothing and its offsets need not be memory (a FRAME buffer of length 0 still
+ * writes its 30-byte frame).  A CRYPT or OPEN buffer may be written in place (out == in and
+ * out_offsets[k] == buf_offsets[k]); otherwise no output range overlaps any input or output range of
+ * the call.
+ * One launch, one lane per stream.  A wave (64 consecutive streams) whose streams are of one kind runs
+ * that kind's code alone; a wave with two or three kinds runs them one after another, which is
+ * correct and slower: group the streams by kind.
+ * Flags, return codes and hip_stream as BRB_RC4_CryptListBatch.  BRB_BATCH_DEVICE (optionally
+ * BRB_BATCH_ASYNC): every pointer is device memory, nothing is allocated (with ASYNC
+ * graph-capturable: GRAPH CAPTURE above) and nothing is validated beyond NULL pointers, the counts and
+ * the flags.  BRB_BATCH_HOST returns -1 with a reason, and writes nothing, for: a NULL required
+ * pointer (salts with a FRAME stream, valid with an OPEN stream); a kind above 2; a
+ * stream_first_buf that decreases; an offset + length (+ 30 for a FRAME output) that wraps; a
+ * state_index entry >= n_states, or one named twice (without state_index: n_streams > n_states); more
+ * streams or buffers than a launch takes; BRB_BATCH_ALL_DEVICES, which this call does not split.
+ * Host mode stages the named states densely in both directions (states not named are neither read
+ * nor written), the span of the inputs, the span of the outputs in both directions (so bytes between
+ * buffers survive), the arrays, and valid over the named buffers in both directions.
+ * n_streams == 0 returns 1 and touches nothing.  Lone waves: BRB_BATCH_FAULT never occurs.  No CPU
+ * fallback: without a usable device the call returns 0 with the reason in BRB_CryptoGPU_LastError(). */
+#define BRB_RC4_KIND_CRYPT 0   /* BRB_RC4_Crypt per buffer                       */
+#define BRB_RC4_KIND_FRAME 1   /* WRITE side of RC4_MD5 per buffer (+30 bytes)    */
+#define BRB_RC4_KIND_OPEN  2   /* READ side of RC4_MD5 + DataValidate per buffer  */
+int BRB_RC4_MixedListBatch(BRB_RC4_State *states, uint64_t n_states, const uint32_t *state_index,
+                           const uint8_t *stream_kind, const void *in, void *out,
+                           const uint64_t *buf_offsets, const uint32_t *buf_lengths,
+                           const uint64_t *out_offsets, const uint64_t *salts,
+                           const uint64_t *stream_first_buf, uint64_t n_streams,
+                           uint8_t *valid, unsigned flags, void *hip_stream);
+
 /* ---- Receive-loop batching ------------------------------------------------------
  * The comm layer calls the transform hook once per buffer on the thread that owns the connection
  * (EvAIOReqTransform_ReadData / _WriteData, ev_kq_aio_transform.c:42-70, from comm_tcp_server.c:1749,
@@ -617,6 +662,22 @@ int BRB_RC4MD5_OpenListBatch(BRB_RC4_State *states, const void *frames, void *ou
  * a batcher without the flag; it combines with the three flags above (an all-devices batcher passes it
  * to its parts).  The list kernels run one wave per 64 connections, not wave pairs. */
 #define BRB_BATCHER_CONN_LISTS    0x800
+/* OR into `algo` at Create: an algo per connection, one launch per round.  The reference fixes a
+ * connection's transform when it is enabled (crypto->algo_code, ev_kq_aio_transform.c:75-108) and a
+ * daemon holds RC4 and RC4_MD5 connections side by side.  With this flag the numeric algo is only the
+ * default that Enable and EnableBatch give a connection; EnableAlgo / EnableBatchAlgo give it its own.
+ * A round is one launch of the mixed kernel (BRB_RC4_MixedListBatch above): every (direction,
+ * connection) is a stream with its buffers in submission order, CRYPT for an RC4 connection in either
+ * direction, OPEN for an RC4_MD5 read, FRAME for an RC4_MD5 write; the streams are sorted by kind, so
+ * all but two waves of a round run one kind.  Read and Write take the connection's algo at submission:
+ * an RC4_MD5 write delivers len + 30 bytes, an RC4 buffer ignores salt and delivers valid = 1, an
+ * RC4_MD5 read delivers the check's verdict.  The flag implies BRB_BATCHER_CONN_LISTS (passing both
+ * changes nothing) and combines with ZERO_COPY, PIPELINED and ALL_DEVICES (passed to the parts).
+ * Enable / EnableBatch on a connection that has another algo than the default return 0, with nothing
+ * changed, while the round being filled holds a buffer of it (as EnableAlgo does for any connection).
+ * Callback order, GetState, key epochs and the dropped-round and poisoning rules are those of every
+ * batcher.  The kernel runs lone waves, not wave pairs. */
+#define BRB_BATCHER_MIXED         0x1000
 typedef struct BRB_TransformBatcher BRB_TransformBatcher;
 typedef void (*BRB_TransformDone)(void *user, uint32_t conn, int op, const void *out, uint32_t out_len, int valid);
 /* `valid` of a buffer whose round was dropped (out = NULL, out_len = 0): see Flush. */
@@ -627,6 +688,20 @@ BRB_TransformBatcher *BRB_TransformBatcherCreate(uint32_t max_conns, uint64_t ma
 void BRB_TransformBatcherDestroy(BRB_TransformBatcher *b);
 /* EvAIOReqTransform_CryptoEnable (ev_kq_aio_transform.c:71-105): both states of `conn` = BRB_RC4_Init(key). */
 int BRB_TransformBatcherEnable(BRB_TransformBatcher *b, uint32_t conn, const void *key, int key_sz);
+/* EvAIOReqTransform_CryptoEnable(transform_info, algo_code, key, key_sz): as Enable, and the
+ * connection's algo becomes `algo` (Enable: the batcher's own).  Returns -1, with nothing changed, for
+ * an algo other than RC4 (1) or RC4_MD5 (2), and for an algo other than the batcher's on a batcher
+ * created without BRB_BATCHER_MIXED.  Returns 0 (BRB_BATCH_NOT_DONE) with a reason, and nothing
+ * changed, when the round being filled holds a buffer of the connection -- it was submitted under
+ * the old key and algo and would run under the new: Flush first. */
+int BRB_TransformBatcherEnableAlgo(BRB_TransformBatcher *b, uint32_t conn, int algo, const void *key, int key_sz);
+/* EvAIOReqTransform_CryptoDisable (ev_kq_aio_transform.c:110-123), on any batcher: both states of
+ * `conn` are zeroed -- on the batcher's stream, so behind a round FlushAsync left running -- and the
+ * connection is not enabled any more: Read / Write refuse it as one never enabled, GetState returns
+ * 264 zero bytes, and Enable / EnableAlgo bring it back, poisoned or not.  Returns 0 with a reason,
+ * and nothing changed, when the round being filled holds a buffer of the connection; -1 for a bad
+ * batcher or connection id. */
+int BRB_TransformBatcherDisable(BRB_TransformBatcher *b, uint32_t conn);
 /* Enable for n connections in one call (host pointers; keys as in BRB_RC4_InitBatch, connection
  * conns[i] gets key i).  One H2D copy of the key bytes and index arrays, one kernel that writes both
  * the read and the write state of every listed connection straight into the batcher's state arrays,
@@ -641,9 +716,17 @@ int BRB_TransformBatcherEnable(BRB_TransformBatcher *b, uint32_t conn, const voi
  * again); the other parts' connections are enabled. */
 int BRB_TransformBatcherEnableBatch(BRB_TransformBatcher *b, const uint32_t *conns, uint64_t n,
                                     const void *keys, const uint64_t *key_offsets, const uint32_t *key_lengths);
+/* EnableBatch with an algo per listed connection (algos[i] = 1 or 2; algos == NULL: the batcher's
+ * own for all): one key-setup kernel, as EnableBatch.  Besides EnableBatch's refusals it returns -1,
+ * with nothing changed, for an algo other than 1 or 2 and for an algo other than the batcher's on a
+ * batcher without BRB_BATCHER_MIXED, and 0 with a reason, and nothing changed, when the round being
+ * filled holds a buffer of a listed connection. */
+int BRB_TransformBatcherEnableBatchAlgo(BRB_TransformBatcher *b, const uint32_t *conns, uint64_t n,
+                                        const uint8_t *algos, const void *keys, const uint64_t *key_offsets,
+                                        const uint32_t *key_lengths);
 /* Read/Write may run concurrently on several threads (the reference's mt_engine, ev_kq_base.c:95)
  * as long as each connection is submitted from one thread; results come back in each connection's
- * order.  Flush/FlushAsync/Enable must not overlap them.  A thread reserves slots and arena bytes in
+ * order.  Flush/FlushAsync/Enable/EnableAlgo/EnableBatch/EnableBatchAlgo/Disable must not overlap them.  A thread reserves slots and arena bytes in
  * chunks, so a round shared by T threads may report full up to T chunks (64 buffers, 128 KiB) early. */
 int BRB_TransformBatcherRead(BRB_TransformBatcher *b, uint32_t conn, const void *data, uint32_t len);
 int BRB_TransformBatcherWrite(BRB_TransformBatcher *b, uint32_t conn, const void *data, uint32_t len, uint64_t salt);
@@ -681,7 +764,8 @@ int BRB_TransformBatcherGetState(BRB_TransformBatcher *b, uint32_t conn, int op,
 /* Test support, not for production use: from now on the `launch`-th kernel launch (0-based) of every
  * round reports a failure without running, so a test can watch a round being dropped; -1 turns it
  * off.  A round launches one kernel per direction and sub-round (READ before WRITE in each sub-round);
- * with BRB_BATCHER_CONN_LISTS one per direction, so at most two.  Returns 1, or -1 for a NULL batcher.  (Replaces round 2's BRB_TEST_BATCHER_FAULT variable:
+ * with BRB_BATCHER_CONN_LISTS one per direction, so at most two; with BRB_BATCHER_MIXED one, so launch = 0
+ * drops the round with nothing run (no state changes, nothing is poisoned) and launch = 1 never fires.  Returns 1, or -1 for a NULL batcher.  (Replaces round 2's BRB_TEST_BATCHER_FAULT variable:
  * the library reads no environment variable.) */
 int BRB_TransformBatcherInjectFault(BRB_TransformBatcher *b, int launch);
 
