@@ -89,12 +89,15 @@ struct Md5Stream : Md5Words {                       // BRB_MD5_CTX: buf[4], byte
     }
 
     // w: the buffered bytes with the 0x80 marker, zeros behind it.  BRB_MD5Final (md5.c:134-168): buf,
-    // digest and string[0 .. 33) are written; bytes, string[33 .. 64) and in are not.
+    // digest and string[0 .. 33) are written, and in is left holding the last block it transformed (the
+    // padded block, or 14 zero words and the bit count when the padding took a block of its own);
+    // bytes and string[33 .. 64) are not written.
     static BRB_DEV void final(uint8_t *cx, uint32_t (&h)[kHdr], uint32_t (&w)[16], uint32_t t, uint8_t *digests, uint64_t i)
     {
         State st = state(h);
         md5_finish(st, w, t, uint64_t(h[4]) | (uint64_t(h[5]) << 32));
         st16_a4(cx, st.a, st.b, st.c, st.d);
+        store_words(cx + 24, w);
         st16_a4(cx + 88, st.a, st.b, st.c, st.d);
         const uint32_t d[4] = {st.a, st.b, st.c, st.d};
         uint32_t hx[8];

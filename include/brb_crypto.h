@@ -307,12 +307,14 @@ int BrbSha1_Batch(const void *data, const uint64_t *offsets, const uint32_t *len
  *   carries from bytes[0] into bytes[1]; SHA-1 adds len << 3 to count[0], carries when the 32-bit sum is
  *   below the untruncated len << 3 (the spurious carry of sha1.c:151 for len >= 2^29 included), then
  *   adds len >> 29 to count[1].  Bytes of in / buffer PAST the buffered count are UNSPECIFIED after
- *   Update (and MD5's in after Final): they may differ from what the compat call leaves there.  No later
+ *   Update: they may differ from what the compat call leaves there.  No later
  *   call, host or batch, reads them before overwriting them.  MD5's digest and string are not touched.
  *   A piece of length 0 changes nothing, and its offset need not be memory.
  * MD5 Final = BRB_MD5Final: buf is the final state, digest its 16 bytes, string[0 .. 33) the lowercase
- *   hex and its NUL; string[33 .. 64) and bytes are untouched; digests[i], when digests is not NULL,
- *   gets the same 16 bytes, in item order.
+ *   hex and its NUL, in the last block the call transformed (the padded block; 14 zero words and the bit
+ *   count when the padding took a block of its own), so the whole struct is the reference's byte for
+ *   byte; string[33 .. 64) and bytes are untouched; digests[i], when digests is not NULL, gets the same
+ *   16 bytes, in item order.
  * SHA-1 Final = BrbSha1_Final: 20 big-endian bytes to digests[i] (required), the whole context zeroed.
  * Flags, return codes, hip_stream and the device-mode contract are BRB_MD5Batch's.  n == 0 returns 1.
  * BRB_BATCH_DEVICE (optionally BRB_BATCH_ASYNC): ctxs, ctx_index, data, offsets, lengths and digests
@@ -359,7 +361,7 @@ int BrbSha1_FinalBatch(BrbSha1Ctx *ctxs, uint64_t n_ctx, const uint32_t *ctx_ind
  *   buffered bytes; bytes of the block buffer past them stay unspecified.  The counters advance once
  *   PER SEGMENT with the reference's own arithmetic, so SHA-1's spurious carry is per segment, as it is
  *   per BrbSha1_Update call.
- * An item with final[i] != 0.  MD5: buf, digest and string[0 .. 33) are as BRB_MD5Final leaves them,
+ * An item with final[i] != 0.  MD5: buf, in, digest and string[0 .. 33) are as BRB_MD5Final leaves them,
  *   bytes as the segments advanced it, string[33 .. 64) untouched; digests[i] is written when digests is
  *   not NULL.  SHA-1: digests[i] is written (digests is required whenever final is not NULL) and the
  *   whole context is zeroed.

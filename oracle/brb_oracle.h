@@ -13,14 +13,14 @@
  * never links, loads or calls this code.
  *
  * Parity pinning (see DESIGN.md "Oracle"):
- *   * The reference build is UNBUILDABLE here: every crypto unit includes libbrb_data.h, which needs
- *     <bsd/string.h>/<bsd/stdlib.h> (libbsd-dev, absent), and stand-in headers are not allowed.
+ *   * Reference output: oracle/ref_build/ builds the reference's own units where a checkout is present;
+ *     tests/golden/ref_run/ holds what they returned and tests/test_ref_run_cpu.py compares every
+ *     function below with it (all 64 bits of every Blowfish word included).
  *   * MD5 / SHA-1: pinned by RFC 1321 A.5 and FIPS 180-1 known answers plus Python hashlib
  *     (OpenSSL), which the survey verified equal to the reference on 20 edge lengths.
  *   * Blowfish: the low 32 bits of every word are pinned by the published Blowfish known answers
  *     (Kocher "TESTKEY", Eric Young ECB set) and by OpenSSL BF_encrypt over random keys.
- *     The HIGH 32 bits (the reference's 64-bit carries) are pinned only by this restatement:
- *     "parity unpinned" for the high halves.
+ *     The HIGH 32 bits (the reference's 64-bit carries) are pinned by the reference-run vectors.
  */
 #ifndef BRB_ORACLE_H
 #define BRB_ORACLE_H

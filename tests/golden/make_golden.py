@@ -17,8 +17,8 @@ Sources, in order of authority (DESIGN.md "Oracle"):
     computed by the Chudnovsky series (the oracle uses BBP digit extraction, the product's header
     Machin's formula).  blowfish64.json is written only if both derivations agree on every word.
 
-The reference itself cannot be built here (libbrb_data.h needs <bsd/string.h>, absent; stand-in
-headers are not allowed), so no fixture comes from running reference code.
+No fixture written here comes from running reference code; those are tests/golden/ref_run/*.json,
+written by tests/golden/make_ref_run.py from a build of the reference's own units.
 
 Usage (in the repo root):  python tests/golden/make_golden.py
 """

@@ -1136,8 +1136,9 @@ class StreamInit(Contexts):
 
 
 class StreamFinal(Contexts):
-    """FinalBatch under a graph: 130 contexts that hold 64 + have bytes.  MD5 gets the final state, the digest
-    and the hex string and keeps its counters and the string's tail; a SHA-1 context is zeroed."""
+    """FinalBatch under a graph: 130 contexts that hold 64 + have bytes.  MD5 gets the final state, the last
+    block BRB_MD5Final transformed (in), the digest and the hex string and keeps its counters and the string's
+    tail; a SHA-1 context is zeroed."""
     carried = ()
 
     def __init__(self, brb, orc, alg):
@@ -1160,5 +1161,5 @@ class StreamFinal(Contexts):
             if self.alg == "sha1":
                 want[i] = 0
             else:
-                want[i, :16], want[i, 88:137] = done[:16], done[88:137]
+                want[i, :16], want[i, 24:137] = done[:16], done[24:137]
         return {"ctxs": want, "out": out}

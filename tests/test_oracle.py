@@ -3,7 +3,8 @@
 The oracle (oracle/brb_oracle.c) is the checker for every GPU parity test, so it is pinned first:
   * MD5: RFC 1321 A.5; SHA-1: FIPS 180-1 A/B/C; both also against hashlib at every edge length.
   * Blowfish: low 32 bits vs Eric Young's ECB vectors, Kocher's TESTKEY and OpenSSL BF_encrypt;
-    high 32 bits: regression fixtures of the restatement only ("parity unpinned").
+    high 32 bits: regression fixtures of the restatement here; pinned by reference output in
+    tests/test_ref_run_cpu.py (tests/golden/ref_run/blowfish.json).
   * pi tables: BBP digit extraction (oracle) == Machin expansion (tools/gen_pi_tables.py).
 """
 import ctypes

@@ -12,8 +12,8 @@ the IV (sha1.c:54-58, 99-118, 132-139).  Here the same hashes are recomputed fro
   * the oracle: orc_bf_pi_words (BBP digits of pi), orc_md5_consts (sin-derived T), orc_sha1_consts;
 
 so a deviation of any of them from the reference's text fails here.  This pins the inputs of the
-64-bit Blowfish high halves to the reference (the halves themselves stay "parity unpinned": no
-reference-run vector exists)."""
+64-bit Blowfish high halves to the reference; the halves themselves are pinned by the reference-run
+vectors of tests/golden/ref_run/ (tests/test_ref_run_cpu.py)."""
 import json
 import os
 import re
