@@ -22,8 +22,12 @@ BRB_DEV uint32_t funnel(uint32_t hi, uint32_t lo, uint32_t sh)
 // Global-memory accessors.  Pointers rebuilt from integers (byte offsets rounded to dwords) lose
 // their address space, and hipcc then emits FLAT instructions, which count in LGKM_CNT as well as
 // VM_CNT: every LDS wait of a kernel (the RC4 generator's) would also wait for its HBM loads and
-// stores.  These casts keep them global_load / global_store.
+// stores.  These casts keep them global_load / global_store.  (BRB_GLOBAL can be predefined empty:
+// the host build of tests/c/lane_io_check.cpp does, because AddressSanitizer does not instrument
+// accesses through a non-default address space.)
+#ifndef BRB_GLOBAL
 #define BRB_GLOBAL __attribute__((address_space(1)))
+#endif
 #define BRB_GPTR(T, p) ((BRB_GLOBAL T *)(uintptr_t)(p))
 typedef uint32_t brb_v4u_a4 __attribute__((ext_vector_type(4), aligned(4)));
 

@@ -137,6 +137,9 @@ struct Snk {
 // (shared with the previous stream) is stored dword by dword, and the dwords left in the row are
 // stored dword by dword before the byte-exact tail (drain).  Rows are 144 bytes apart (36 banks):
 // lanes writing the same row position meet at most 4-way.
+// The row positions (ta, tb) are fixed at init() for blocks that start a multiple of 16 chunks into the
+// stream: single put()s come only after the last put16() -- whole blocks, then the tail, as the RC4
+// kernels feed it.  (Snk takes both in any order.)
 struct SectorSnk {
     static constexpr uint32_t kRowBytes = 144;
     Snk s;                     // the byte-exact ends and the current position
