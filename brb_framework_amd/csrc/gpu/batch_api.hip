@@ -211,6 +211,21 @@ Span span_rebase(const uint64_t *offs, const LenT *lens, uint64_t n, uint64_t ex
     return sp;
 }
 
+// The data segments of a call that reads `in` and writes `out`, which may be the same bytes: in place, one
+// segment staged in both directions; else the input in and the output in both directions, so that the bytes
+// of the output's span the call does not write survive.
+struct InOut { size_t in, out; };
+
+InOut stage_in_out(Staging &st, bool in_place, const uint8_t *in, size_t in_bytes, uint8_t *out, size_t out_bytes)
+{
+    if (in_place) {
+        const size_t i = st.inout(out, out_bytes);
+        return {i, i};
+    }
+    const size_t i = st.in(in, in_bytes);
+    return {i, st.inout(out, out_bytes)};
+}
+
 // BRB_BATCH_ALL_DEVICES for the multi-range calls whose host-mode parts write a byte span back
 // (RC4 streams, frames, base64 outputs): part g stages and returns the span its ranges
 // [g n/G, (g+1) n/G) cover, so the split is taken only when those spans are pairwise disjoint --
@@ -271,30 +286,12 @@ FirstList first_list(const uint64_t *first, uint64_t n, const char *name, Each e
     return fl;
 }
 
-FirstList first_list(const uint64_t *first, uint64_t n, const char *name)
+// count_items: the range must also fit one launch (items_ok: the RC4 list kernels' per-buffer arrays)
+FirstList first_list(const uint64_t *first, uint64_t n, const char *name, bool count_items = false)
 {
-    return first_list(first, n, name, [](uint64_t) { return true; });
-}
-
-// The buffers a host-mode RC4 list call names: stream_first_buf checked (non-decreasing, no more buffers
-// than a launch takes), the range [k0, k0 + count) of the per-buffer arrays and the list rebased to 0.
-struct BufList {
-    bool ok = false;
-    uint64_t k0 = 0, count = 0;
-    std::vector<uint64_t> first;
-};
-
-BufList buf_list(const uint64_t *first, uint64_t n)
-{
-    BufList bl;
-    const FirstList fl = first_list(first, n, "stream_first_buf");
-    if (!fl.ok || !items_ok(fl.count))
-        return bl;
-    bl.ok = true;
-    bl.k0 = fl.k0;
-    bl.count = fl.count;
-    bl.first = fl.rebased();
-    return bl;
+    FirstList fl = first_list(first, n, name, [](uint64_t) { return true; });
+    fl.ok = fl.ok && (!count_items || items_ok(fl.count));
+    return fl;
 }
 
 // parts_disjoint for streams that own buffer lists: stream i's written span is the span of buffers
@@ -1023,304 +1020,135 @@ int membuf_batch(void *data, const uint64_t *buf_offsets, const uint64_t *sizes,
     return rc;
 }
 
+// ---- RC4, RC4+MD5 frame and RC4+MD5 open (rc4_kernels.hip, rc4_list_kernels.hip) -------------------
+// BRB_RC4_CryptBatch, BRB_RC4MD5_FrameBatch, BRB_RC4MD5_OpenBatch (a buffer per stream) and their List forms
+// (stream i owns buffers first[i] .. first[i + 1] - 1 of the per-buffer arrays).  `c` holds the caller's
+// arguments as the launch takes them (brb::Rc4Launch; ooffs = the frame offsets), so device mode launches it
+// as it stands.  Host mode stages, of buffers [fl.k0, fl.k0 + fl.count): the n states and the outputs' span in
+// both directions, the inputs' span (sp; frames: sf) and the lengths, salts and rebased offsets in, valid out.
+// The single-buffer form is the list form over buffers [0, n) with no list staged (rfirst NULL).
+int rc4_stage(const brb::Rc4Launch &c, const FirstList &fl, const Span &sp, const Span &sf, const uint64_t *rfirst,
+              const PairFault *pf, hipStream_t s)
+{
+    const bool frame = c.kind == BRB_RC4_KIND_FRAME, open = c.kind == BRB_RC4_KIND_OPEN;
+    const uint64_t n = c.n, k0 = fl.k0, count = fl.count;
+    const Span &so = frame ? sf : sp;               // crypt and open write at the inputs' offsets in `out`
+    Staging st;
+    const size_t i_st = st.inout(c.states, sizeof(BRB_RC4_State) * n);
+    const InOut io = stage_in_out(st, !frame && c.in == c.out, c.in + sp.lo, sp.bytes(), c.out + so.lo, so.bytes());
+    const size_t i_off = st.in(sp.off.data(), 8 * count);
+    const size_t i_fo = frame ? st.in(sf.off.data(), 8 * count) : 0;
+    const size_t i_len = st.in(c.lens + k0, 4 * count);
+    const size_t i_salt = frame ? st.in(c.salts + k0, 8 * count) : 0;
+    const size_t i_first = rfirst ? st.in(rfirst, 8 * (n + 1)) : 0;
+    const size_t i_val = open ? st.out(c.valid + k0, count) : 0;
+    return st.run(s, pf, [&] {
+        brb::Rc4Launch l = c;                        // the kind and the count; every pointer is the staged copy's
+        l.states = st.dev(i_st);
+        l.in = st.dev(io.in);
+        l.out = st.dev(io.out);
+        l.offs = st.dev<uint64_t>(i_off);
+        l.lens = st.dev<uint32_t>(i_len);
+        l.ooffs = frame ? st.dev<uint64_t>(i_fo) : nullptr;
+        l.salts = frame ? st.dev<uint64_t>(i_salt) : nullptr;
+        l.first = rfirst ? st.dev<uint64_t>(i_first) : nullptr;
+        l.valid = open ? st.dev(i_val) : nullptr;
+        return launched(brb::launch_rc4(l, s));
+    });
+}
+
+// The two forms take their refusals in different orders, and each keeps its own.  A buffer per stream: NULL
+// pointers, counts and flags, the device, the all-devices split, the fault word (wave-pair kernels), then
+// device mode launches and host mode looks at the ranges.  List: NULL pointers, counts and flags, then device
+// mode probes and launches (lone waves: no fault word) and host mode checks everything -- the list, the
+// ranges -- before any device work: the device, the all-devices split, the staging.  nulls: the NULL refusal.
+int rc4_batch(const brb::Rc4Launch &c, bool list, const char *nulls, unsigned flags, void *stream)
+{
+    t_err.clear();
+    const uint64_t n = c.n;
+    if (n == 0)
+        return BRB_BATCH_OK;
+    const bool frame = c.kind == BRB_RC4_KIND_FRAME, open = c.kind == BRB_RC4_KIND_OPEN;
+    if (!c.states || !c.in || !c.out || !c.offs || !c.lens || (list && !c.first) || (frame && (!c.salts || !c.ooffs)) ||
+        (open && !c.valid)) {
+        set_err("%s", nulls);
+        return BRB_BATCH_BADARG;
+    }
+    if (!items_ok(n) || !flags_ok(flags))
+        return BRB_BATCH_BADARG;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const bool device = (flags & BRB_BATCH_DEVICE) != 0;
+    FirstList fl{c.first, n, 0, n, true};           // a buffer per stream: buffer i is stream i's
+    Span sp, sf;
+    // the list form stops at the first range that wraps; the other looks at both spans (the later text stands)
+    auto spans = [&] {
+        sp = span_rebase(c.offs + fl.k0, c.lens + fl.k0, fl.count);
+        if (frame && (sp.ok || !list))
+            sf = span_rebase(c.ooffs + fl.k0, c.lens + fl.k0, fl.count, BRB_RC4MD5_HEADER);
+        return sp.ok && (!frame || sf.ok);
+    };
+    if (list && !device) {
+        fl = first_list(c.first, n, "stream_first_buf", true);
+        if (!fl.ok || !spans())
+            return BRB_BATCH_BADARG;
+    }
+    if (int ok = device_ok(); ok != BRB_BATCH_OK)
+        return ok;
+    if (list && device)
+        return device_run(brb::launch_rc4(c, s), s, flags);
+    if (flags & BRB_BATCH_ALL_DEVICES) {   // streams split over the devices, their states and buffers with them
+        flags &= ~BRB_BATCH_ALL_DEVICES;
+        // what a part writes is copied back: the parts' spans (frames: of the frames) must not interleave
+        const uint64_t *woffs = frame ? c.ooffs : c.offs;
+        const uint64_t extra = frame ? BRB_RC4MD5_HEADER : 0;
+        if (list ? stream_parts_disjoint(woffs, c.lens, c.first, n, extra) : parts_disjoint(woffs, c.lens, n, extra))
+            return brb_host::split_devices(n, [&](int, uint64_t lo, uint64_t hi) {
+                brb::Rc4Launch p = c;
+                p.states += lo * sizeof(BRB_RC4_State);
+                p.n = hi - lo;
+                if (list) {
+                    p.first += lo;                   // the per-buffer arrays stay: the list names the part's range
+                } else {
+                    p.offs += lo;
+                    p.lens += lo;
+                    p.ooffs = frame ? c.ooffs + lo : nullptr;
+                    p.salts = frame ? c.salts + lo : nullptr;
+                    p.valid = open ? c.valid + lo : nullptr;
+                }
+                return rc4_batch(p, list, nulls, flags, nullptr);
+            });
+    }
+    if (list)
+        return rc4_stage(c, fl, sp, sf, fl.rebased().data(), nullptr, s);
+    const PairFault pf(flags);                       // pair_fault.h
+    if (int ok = pf.ready(); ok != BRB_BATCH_OK)
+        return ok;
+    if (device)
+        return device_run(brb::launch_rc4(c, s), s, flags, &pf);
+    if (!spans())
+        return BRB_BATCH_BADARG;
+    return rc4_stage(c, fl, sp, sf, nullptr, &pf, s);
+}
+
+// the caller's arguments of the six calls as a launch; the wrappers add salts, frame offsets and valid
+brb::Rc4Launch rc4_args(int kind, BRB_RC4_State *states, const void *in, void *out, const uint64_t *offs,
+                        const uint32_t *lens, const uint64_t *first, uint64_t n)
+{
+    brb::Rc4Launch c;
+    c.kind = kind;
+    c.states = reinterpret_cast<uint8_t *>(states);
+    c.in = bytes(in);
+    c.out = bytes(out);
+    c.offs = offs;
+    c.lens = lens;
+    c.first = first;
+    c.n = n;
+    return c;
+}
+
 }  // namespace
 
 extern "C" {
-
-int BRB_RC4_CryptBatch(BRB_RC4_State *states, const void *in, void *out, const uint64_t *offsets, const uint32_t *lengths,
-                       uint64_t n, unsigned flags, void *stream)
-{
-    t_err.clear();
-    if (n == 0)
-        return BRB_BATCH_OK;
-    if (!states || !in || !out || !offsets || !lengths) {
-        set_err("NULL states, in, out, offsets or lengths");
-        return BRB_BATCH_BADARG;
-    }
-    if (!items_ok(n) || !flags_ok(flags))
-        return BRB_BATCH_BADARG;
-    if (int ok = device_ok(); ok != BRB_BATCH_OK)
-        return ok;
-    if (flags & BRB_BATCH_ALL_DEVICES) {   // connections split over the devices, states with them
-        flags &= ~BRB_BATCH_ALL_DEVICES;
-        if (parts_disjoint(offsets, lengths, n, 0))
-            return brb_host::split_devices(n, [&](int, uint64_t lo, uint64_t hi) {
-                return BRB_RC4_CryptBatch(states + lo, in, out, offsets + lo, lengths + lo, hi - lo, flags, nullptr);
-            });
-    }
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const PairFault pf(flags);                       // pair_fault.h
-    if (int ok = pf.ready(); ok != BRB_BATCH_OK)
-        return ok;
-    if (flags & BRB_BATCH_DEVICE)
-        return device_run(brb::launch_rc4_crypt(bytes(states), bytes(in), bytes(out), offsets, lengths, n, s), s, flags, &pf);
-    const Span sp = span_rebase(offsets, lengths, n);
-    if (!sp.ok)
-        return BRB_BATCH_BADARG;
-    Staging st;
-    const size_t i_st = st.inout(states, sizeof(BRB_RC4_State) * n);
-    // a separate output buffer is staged with its current bytes so that bytes outside the streams survive
-    const size_t i_in = in == out ? st.inout(bytes(out) + sp.lo, sp.bytes()) : st.in(bytes(in) + sp.lo, sp.bytes());
-    const size_t i_out = in == out ? i_in : st.inout(bytes(out) + sp.lo, sp.bytes());
-    const size_t i_off = st.in(sp.off.data(), 8 * n);
-    const size_t i_len = st.in(lengths, 4 * n);
-    return st.run(s, &pf, [&] {
-        return launched(brb::launch_rc4_crypt(st.dev(i_st), st.dev(i_in), st.dev(i_out), st.dev<uint64_t>(i_off),
-                                              st.dev<uint32_t>(i_len), n, s));
-    });
-}
-
-int BRB_RC4MD5_FrameBatch(BRB_RC4_State *states, const void *payload, const uint64_t *offsets, const uint32_t *lengths,
-                          const uint64_t *salts, void *frames, const uint64_t *frame_offsets, uint64_t n, unsigned flags,
-                          void *stream)
-{
-    t_err.clear();
-    if (n == 0)
-        return BRB_BATCH_OK;
-    if (!states || !payload || !offsets || !lengths || !salts || !frames || !frame_offsets) {
-        set_err("NULL states, payload, offsets, lengths, salts, frames or frame_offsets");
-        return BRB_BATCH_BADARG;
-    }
-    if (!items_ok(n) || !flags_ok(flags))
-        return BRB_BATCH_BADARG;
-    if (int ok = device_ok(); ok != BRB_BATCH_OK)
-        return ok;
-    if (flags & BRB_BATCH_ALL_DEVICES) {   // frames are written back: their spans must not interleave
-        flags &= ~BRB_BATCH_ALL_DEVICES;
-        if (parts_disjoint(frame_offsets, lengths, n, BRB_RC4MD5_HEADER))
-            return brb_host::split_devices(n, [&](int, uint64_t lo, uint64_t hi) {
-                return BRB_RC4MD5_FrameBatch(states + lo, payload, offsets + lo, lengths + lo, salts + lo, frames,
-                                             frame_offsets + lo, hi - lo, flags, nullptr);
-            });
-    }
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const PairFault pf(flags);                       // pair_fault.h
-    if (int ok = pf.ready(); ok != BRB_BATCH_OK)
-        return ok;
-    if (flags & BRB_BATCH_DEVICE)
-        return device_run(brb::launch_rc4md5_frame(bytes(states), bytes(payload), offsets, lengths, salts, bytes(frames),
-                                                   frame_offsets, n, s),
-                          s, flags, &pf);
-    const Span sp = span_rebase(offsets, lengths, n), sf = span_rebase(frame_offsets, lengths, n, BRB_RC4MD5_HEADER);
-    if (!sp.ok || !sf.ok)
-        return BRB_BATCH_BADARG;
-    Staging st;
-    const size_t i_st = st.inout(states, sizeof(BRB_RC4_State) * n);
-    const size_t i_pl = st.in(bytes(payload) + sp.lo, sp.bytes());
-    const size_t i_fr = st.inout(bytes(frames) + sf.lo, sf.bytes());
-    const size_t i_po = st.in(sp.off.data(), 8 * n);
-    const size_t i_fo = st.in(sf.off.data(), 8 * n);
-    const size_t i_len = st.in(lengths, 4 * n);
-    const size_t i_salt = st.in(salts, 8 * n);
-    return st.run(s, &pf, [&] {
-        return launched(brb::launch_rc4md5_frame(st.dev(i_st), st.dev(i_pl), st.dev<uint64_t>(i_po), st.dev<uint32_t>(i_len),
-                                                 st.dev<uint64_t>(i_salt), st.dev(i_fr), st.dev<uint64_t>(i_fo), n, s));
-    });
-}
-
-int BRB_RC4MD5_OpenBatch(BRB_RC4_State *states, const void *frames, void *out, const uint64_t *offsets,
-                         const uint32_t *lengths, uint64_t n, uint8_t *valid, unsigned flags, void *stream)
-{
-    t_err.clear();
-    if (n == 0)
-        return BRB_BATCH_OK;
-    if (!states || !frames || !out || !offsets || !lengths || !valid) {
-        set_err("NULL states, frames, out, offsets, lengths or valid");
-        return BRB_BATCH_BADARG;
-    }
-    if (!items_ok(n) || !flags_ok(flags))
-        return BRB_BATCH_BADARG;
-    if (int ok = device_ok(); ok != BRB_BATCH_OK)
-        return ok;
-    if (flags & BRB_BATCH_ALL_DEVICES) {
-        flags &= ~BRB_BATCH_ALL_DEVICES;
-        if (parts_disjoint(offsets, lengths, n, 0))
-            return brb_host::split_devices(n, [&](int, uint64_t lo, uint64_t hi) {
-                return BRB_RC4MD5_OpenBatch(states + lo, frames, out, offsets + lo, lengths + lo, hi - lo, valid + lo, flags,
-                                            nullptr);
-            });
-    }
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const PairFault pf(flags);                       // pair_fault.h
-    if (int ok = pf.ready(); ok != BRB_BATCH_OK)
-        return ok;
-    if (flags & BRB_BATCH_DEVICE)
-        return device_run(brb::launch_rc4md5_open(bytes(states), bytes(frames), bytes(out), offsets, lengths, n, valid, s), s,
-                          flags, &pf);
-    const Span sp = span_rebase(offsets, lengths, n);
-    if (!sp.ok)
-        return BRB_BATCH_BADARG;
-    Staging st;
-    const size_t i_st = st.inout(states, sizeof(BRB_RC4_State) * n);
-    const size_t i_in = frames == out ? st.inout(bytes(out) + sp.lo, sp.bytes()) : st.in(bytes(frames) + sp.lo, sp.bytes());
-    const size_t i_out = frames == out ? i_in : st.inout(bytes(out) + sp.lo, sp.bytes());
-    const size_t i_off = st.in(sp.off.data(), 8 * n);
-    const size_t i_len = st.in(lengths, 4 * n);
-    const size_t i_val = st.out(valid, n);
-    return st.run(s, &pf, [&] {
-        return launched(brb::launch_rc4md5_open(st.dev(i_st), st.dev(i_in), st.dev(i_out), st.dev<uint64_t>(i_off),
-                                                st.dev<uint32_t>(i_len), n, st.dev(i_val), s));
-    });
-}
-
-// ---- RC4 over a buffer list per stream (rc4_list_kernels.hip) ------------------------------------
-// Stream i owns buffers first[i] .. first[i + 1] - 1 of the per-buffer arrays.  The kernels are lone
-// waves: no PairFault.  Host mode checks everything before any device work.
-
-int BRB_RC4_CryptListBatch(BRB_RC4_State *states, const void *in, void *out, const uint64_t *offsets,
-                           const uint32_t *lengths, const uint64_t *first, uint64_t n, unsigned flags, void *stream)
-{
-    t_err.clear();
-    if (n == 0)
-        return BRB_BATCH_OK;
-    if (!states || !in || !out || !offsets || !lengths || !first) {
-        set_err("NULL states, in, out, buf_offsets, buf_lengths or stream_first_buf");
-        return BRB_BATCH_BADARG;
-    }
-    if (!items_ok(n) || !flags_ok(flags))
-        return BRB_BATCH_BADARG;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (flags & BRB_BATCH_DEVICE) {
-        if (int ok = device_ok(); ok != BRB_BATCH_OK)
-            return ok;
-        return device_run(brb::launch_rc4_crypt_list(bytes(states), bytes(in), bytes(out), offsets, lengths, first, n, s), s,
-                          flags);
-    }
-    const BufList bl = buf_list(first, n);
-    if (!bl.ok)
-        return BRB_BATCH_BADARG;
-    const Span sp = span_rebase(offsets + bl.k0, lengths + bl.k0, bl.count);
-    if (!sp.ok)
-        return BRB_BATCH_BADARG;
-    if (int ok = device_ok(); ok != BRB_BATCH_OK)
-        return ok;
-    if (flags & BRB_BATCH_ALL_DEVICES) {   // streams split over the devices, states and buffer ranges with them
-        flags &= ~BRB_BATCH_ALL_DEVICES;
-        if (stream_parts_disjoint(offsets, lengths, first, n, 0))
-            return brb_host::split_devices(n, [&](int, uint64_t lo, uint64_t hi) {
-                return BRB_RC4_CryptListBatch(states + lo, in, out, offsets, lengths, first + lo, hi - lo, flags, nullptr);
-            });
-    }
-    Staging st;
-    const size_t i_st = st.inout(states, sizeof(BRB_RC4_State) * n);
-    // a separate output buffer is staged with its current bytes so that bytes outside the buffers survive
-    const size_t i_in = in == out ? st.inout(bytes(out) + sp.lo, sp.bytes()) : st.in(bytes(in) + sp.lo, sp.bytes());
-    const size_t i_out = in == out ? i_in : st.inout(bytes(out) + sp.lo, sp.bytes());
-    const size_t i_off = st.in(sp.off.data(), 8 * bl.count);
-    const size_t i_len = st.in(lengths + bl.k0, 4 * bl.count);
-    const size_t i_first = st.in(bl.first.data(), 8 * (n + 1));
-    return st.run(s, nullptr, [&] {
-        return launched(brb::launch_rc4_crypt_list(st.dev(i_st), st.dev(i_in), st.dev(i_out), st.dev<uint64_t>(i_off),
-                                                   st.dev<uint32_t>(i_len), st.dev<uint64_t>(i_first), n, s));
-    });
-}
-
-int BRB_RC4MD5_FrameListBatch(BRB_RC4_State *states, const void *payload, const uint64_t *offsets, const uint32_t *lengths,
-                              const uint64_t *salts, void *frames, const uint64_t *frame_offsets, const uint64_t *first,
-                              uint64_t n, unsigned flags, void *stream)
-{
-    t_err.clear();
-    if (n == 0)
-        return BRB_BATCH_OK;
-    if (!states || !payload || !offsets || !lengths || !salts || !frames || !frame_offsets || !first) {
-        set_err("NULL states, payload, buf_offsets, buf_lengths, salts, frames, frame_offsets or stream_first_buf");
-        return BRB_BATCH_BADARG;
-    }
-    if (!items_ok(n) || !flags_ok(flags))
-        return BRB_BATCH_BADARG;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (flags & BRB_BATCH_DEVICE) {
-        if (int ok = device_ok(); ok != BRB_BATCH_OK)
-            return ok;
-        return device_run(brb::launch_rc4md5_frame_list(bytes(states), bytes(payload), offsets, lengths, salts, bytes(frames),
-                                                        frame_offsets, first, n, s),
-                          s, flags);
-    }
-    const BufList bl = buf_list(first, n);
-    if (!bl.ok)
-        return BRB_BATCH_BADARG;
-    const Span sp = span_rebase(offsets + bl.k0, lengths + bl.k0, bl.count);
-    if (!sp.ok)
-        return BRB_BATCH_BADARG;
-    const Span sf = span_rebase(frame_offsets + bl.k0, lengths + bl.k0, bl.count, BRB_RC4MD5_HEADER);
-    if (!sf.ok)
-        return BRB_BATCH_BADARG;
-    if (int ok = device_ok(); ok != BRB_BATCH_OK)
-        return ok;
-    if (flags & BRB_BATCH_ALL_DEVICES) {   // frames are written back: the parts' frame spans must not interleave
-        flags &= ~BRB_BATCH_ALL_DEVICES;
-        if (stream_parts_disjoint(frame_offsets, lengths, first, n, BRB_RC4MD5_HEADER))
-            return brb_host::split_devices(n, [&](int, uint64_t lo, uint64_t hi) {
-                return BRB_RC4MD5_FrameListBatch(states + lo, payload, offsets, lengths, salts, frames, frame_offsets,
-                                                 first + lo, hi - lo, flags, nullptr);
-            });
-    }
-    Staging st;
-    const size_t i_st = st.inout(states, sizeof(BRB_RC4_State) * n);
-    const size_t i_pl = st.in(bytes(payload) + sp.lo, sp.bytes());
-    const size_t i_fr = st.inout(bytes(frames) + sf.lo, sf.bytes());
-    const size_t i_po = st.in(sp.off.data(), 8 * bl.count);
-    const size_t i_fo = st.in(sf.off.data(), 8 * bl.count);
-    const size_t i_len = st.in(lengths + bl.k0, 4 * bl.count);
-    const size_t i_salt = st.in(salts + bl.k0, 8 * bl.count);
-    const size_t i_first = st.in(bl.first.data(), 8 * (n + 1));
-    return st.run(s, nullptr, [&] {
-        return launched(brb::launch_rc4md5_frame_list(st.dev(i_st), st.dev(i_pl), st.dev<uint64_t>(i_po),
-                                                      st.dev<uint32_t>(i_len), st.dev<uint64_t>(i_salt), st.dev(i_fr),
-                                                      st.dev<uint64_t>(i_fo), st.dev<uint64_t>(i_first), n, s));
-    });
-}
-
-int BRB_RC4MD5_OpenListBatch(BRB_RC4_State *states, const void *frames, void *out, const uint64_t *offsets,
-                             const uint32_t *lengths, const uint64_t *first, uint64_t n, uint8_t *valid, unsigned flags,
-                             void *stream)
-{
-    t_err.clear();
-    if (n == 0)
-        return BRB_BATCH_OK;
-    if (!states || !frames || !out || !offsets || !lengths || !first || !valid) {
-        set_err("NULL states, frames, out, buf_offsets, buf_lengths, stream_first_buf or valid");
-        return BRB_BATCH_BADARG;
-    }
-    if (!items_ok(n) || !flags_ok(flags))
-        return BRB_BATCH_BADARG;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (flags & BRB_BATCH_DEVICE) {
-        if (int ok = device_ok(); ok != BRB_BATCH_OK)
-            return ok;
-        return device_run(brb::launch_rc4md5_open_list(bytes(states), bytes(frames), bytes(out), offsets, lengths, first, n,
-                                                       valid, s),
-                          s, flags);
-    }
-    const BufList bl = buf_list(first, n);
-    if (!bl.ok)
-        return BRB_BATCH_BADARG;
-    const Span sp = span_rebase(offsets + bl.k0, lengths + bl.k0, bl.count);
-    if (!sp.ok)
-        return BRB_BATCH_BADARG;
-    if (int ok = device_ok(); ok != BRB_BATCH_OK)
-        return ok;
-    if (flags & BRB_BATCH_ALL_DEVICES) {
-        flags &= ~BRB_BATCH_ALL_DEVICES;
-        if (stream_parts_disjoint(offsets, lengths, first, n, 0))
-            return brb_host::split_devices(n, [&](int, uint64_t lo, uint64_t hi) {
-                return BRB_RC4MD5_OpenListBatch(states + lo, frames, out, offsets, lengths, first + lo, hi - lo, valid, flags,
-                                                nullptr);
-            });
-    }
-    Staging st;
-    const size_t i_st = st.inout(states, sizeof(BRB_RC4_State) * n);
-    const size_t i_in = frames == out ? st.inout(bytes(out) + sp.lo, sp.bytes()) : st.in(bytes(frames) + sp.lo, sp.bytes());
-    const size_t i_out = frames == out ? i_in : st.inout(bytes(out) + sp.lo, sp.bytes());
-    const size_t i_off = st.in(sp.off.data(), 8 * bl.count);
-    const size_t i_len = st.in(lengths + bl.k0, 4 * bl.count);
-    const size_t i_first = st.in(bl.first.data(), 8 * (n + 1));
-    const size_t i_val = st.out(valid + bl.k0, bl.count);
-    return st.run(s, nullptr, [&] {
-        return launched(brb::launch_rc4md5_open_list(st.dev(i_st), st.dev(i_in), st.dev(i_out), st.dev<uint64_t>(i_off),
-                                                     st.dev<uint32_t>(i_len), st.dev<uint64_t>(i_first), n, st.dev(i_val), s));
-    });
-}
 
 // Streams of mixed kind (rc4_mixed_kernels.hip): stream i is of kind[i] and uses states[sidx ? sidx[i] : i].
 // Host mode: NamedCtx stages the named states densely, so the kernel runs without an index; the inputs'
@@ -1348,9 +1176,13 @@ int BRB_RC4_MixedListBatch(BRB_RC4_State *states, uint64_t n_states, const uint3
     if (flags & BRB_BATCH_DEVICE) {
         if (int ok = device_ok(); ok != BRB_BATCH_OK)
             return ok;
-        return device_run(brb::launch_rc4_mixed_list(bytes(states), kind, bytes(in), bytes(out), offsets, lengths, out_offsets,
-                                                     salts, first, n, valid, s, sidx),
-                          s, flags);
+        brb::Rc4Launch l = rc4_args(0, states, in, out, offsets, lengths, first, n);
+        l.kinds = kind;
+        l.sidx = sidx;
+        l.ooffs = out_offsets;
+        l.salts = salts;
+        l.valid = valid;
+        return device_run(brb::launch_rc4(l, s), s, flags);
     }
     // host mode: every list is host memory and is checked before anything runs
     bool any_frame = false, any_open = false;
@@ -1366,29 +1198,31 @@ int BRB_RC4_MixedListBatch(BRB_RC4_State *states, uint64_t n_states, const uint3
         set_err(any_frame && !salts ? "NULL salts with a FRAME stream" : "NULL valid with an OPEN stream");
         return BRB_BATCH_BADARG;
     }
-    const BufList bl = buf_list(first, n);
-    if (!bl.ok)
+    const FirstList fl = first_list(first, n, "stream_first_buf", true);
+    if (!fl.ok)
         return BRB_BATCH_BADARG;
+    const uint64_t k0 = fl.k0, count = fl.count;
+    const std::vector<uint64_t> rfirst = fl.rebased();
     NamedCtx named{bytes(states), sidx, n, sizeof(BRB_RC4_State), {}};
     if (!named.ok(n_states, "a connection's buffers of one call go in its stream's list"))
         return BRB_BATCH_BADARG;
-    std::vector<uint64_t> olen(bl.count);   // bytes written per buffer
+    std::vector<uint64_t> olen(count);   // bytes written per buffer
     for (uint64_t i = 0; i < n; i++)
-        for (uint64_t k = bl.first[i]; k < bl.first[i + 1]; k++)
-            olen[k] = uint64_t(lengths[bl.k0 + k]) + (kind[i] == BRB_RC4_KIND_FRAME ? BRB_RC4MD5_HEADER : 0);
-    Span sp = span_rebase(offsets + bl.k0, lengths + bl.k0, bl.count);
+        for (uint64_t k = rfirst[i]; k < rfirst[i + 1]; k++)
+            olen[k] = uint64_t(lengths[k0 + k]) + (kind[i] == BRB_RC4_KIND_FRAME ? BRB_RC4MD5_HEADER : 0);
+    Span sp = span_rebase(offsets + k0, lengths + k0, count);
     if (!sp.ok)
         return BRB_BATCH_BADARG;
-    Span so = span_rebase(out_offsets + bl.k0, olen.data(), bl.count);
+    Span so = span_rebase(out_offsets + k0, olen.data(), count);
     if (!so.ok)
         return BRB_BATCH_BADARG;
     if (int ok = device_ok(); ok != BRB_BATCH_OK)
         return ok;
-    const bool same = in == out;
-    if (same && sp.bytes() && so.bytes()) {   // in place: one span, staged in both directions
+    const bool in_place = in == out && sp.bytes() && so.bytes();
+    if (in_place) {   // one span, staged in both directions
         const uint64_t lo = std::min(sp.lo, so.lo), hi = std::max(sp.hi, so.hi);
-        for (uint64_t k = 0; k < bl.count; k++) {
-            sp.off[k] += lengths[bl.k0 + k] ? sp.lo - lo : 0;
+        for (uint64_t k = 0; k < count; k++) {
+            sp.off[k] += lengths[k0 + k] ? sp.lo - lo : 0;
             so.off[k] += olen[k] ? so.lo - lo : 0;
         }
         sp.lo = so.lo = lo;
@@ -1396,20 +1230,28 @@ int BRB_RC4_MixedListBatch(BRB_RC4_State *states, uint64_t n_states, const uint3
     }
     Staging st;
     const size_t i_st = st.inout(named.gather(), sizeof(BRB_RC4_State) * n);
-    const size_t i_out = st.inout(bytes(out) + so.lo, so.bytes());
-    const size_t i_in = same && sp.bytes() && so.bytes() ? i_out : st.in(bytes(in) + sp.lo, sp.bytes());
-    const size_t i_off = st.in(sp.off.data(), 8 * bl.count);
-    const size_t i_ooff = st.in(so.off.data(), 8 * bl.count);
-    const size_t i_len = st.in(lengths + bl.k0, 4 * bl.count);
-    const size_t i_salt = any_frame ? st.in(salts + bl.k0, 8 * bl.count) : 0;
-    const size_t i_first = st.in(bl.first.data(), 8 * (n + 1));
+    const InOut io = stage_in_out(st, in_place, bytes(in) + sp.lo, sp.bytes(), bytes(out) + so.lo, so.bytes());
+    const size_t i_off = st.in(sp.off.data(), 8 * count);
+    const size_t i_ooff = st.in(so.off.data(), 8 * count);
+    const size_t i_len = st.in(lengths + k0, 4 * count);
+    const size_t i_salt = any_frame ? st.in(salts + k0, 8 * count) : 0;
+    const size_t i_first = st.in(rfirst.data(), 8 * (n + 1));
     const size_t i_kind = st.in(kind, n);
-    const size_t i_val = any_open ? st.inout(valid + bl.k0, bl.count) : 0;
+    const size_t i_val = any_open ? st.inout(valid + k0, count) : 0;
     return named.scatter(st.run(s, nullptr, [&] {
-        return launched(brb::launch_rc4_mixed_list(st.dev(i_st), st.dev(i_kind), st.dev(i_in), st.dev(i_out),
-                                                   st.dev<uint64_t>(i_off), st.dev<uint32_t>(i_len), st.dev<uint64_t>(i_ooff),
-                                                   any_frame ? st.dev<uint64_t>(i_salt) : nullptr, st.dev<uint64_t>(i_first), n,
-                                                   any_open ? st.dev(i_val) : nullptr, s));
+        brb::Rc4Launch l;
+        l.kinds = st.dev(i_kind);
+        l.states = st.dev(i_st);
+        l.in = st.dev(io.in);
+        l.out = st.dev(io.out);
+        l.offs = st.dev<uint64_t>(i_off);
+        l.lens = st.dev<uint32_t>(i_len);
+        l.ooffs = st.dev<uint64_t>(i_ooff);
+        l.salts = any_frame ? st.dev<uint64_t>(i_salt) : nullptr;
+        l.first = st.dev<uint64_t>(i_first);
+        l.n = n;
+        l.valid = any_open ? st.dev(i_val) : nullptr;
+        return launched(brb::launch_rc4(l, s));
     }));
 }
 
@@ -1755,6 +1597,60 @@ int BRB_Blowfish_InitBatch(BRB_BLOWFISH_CTX *ctxs, const void *keys, const uint6
                            const uint32_t *key_lengths, uint64_t n_keys, unsigned flags, void *hip_stream)
 {
     return keysetup_batch(true, ctxs, keys, key_offsets, key_lengths, n_keys, flags, hip_stream);
+}
+
+int BRB_RC4_CryptBatch(BRB_RC4_State *states, const void *in, void *out, const uint64_t *offsets, const uint32_t *lengths,
+                       uint64_t n, unsigned flags, void *hip_stream)
+{
+    return rc4_batch(rc4_args(BRB_RC4_KIND_CRYPT, states, in, out, offsets, lengths, nullptr, n), false,
+                     "NULL states, in, out, offsets or lengths", flags, hip_stream);
+}
+
+int BRB_RC4MD5_FrameBatch(BRB_RC4_State *states, const void *payload, const uint64_t *offsets, const uint32_t *lengths,
+                          const uint64_t *salts, void *frames, const uint64_t *frame_offsets, uint64_t n, unsigned flags,
+                          void *hip_stream)
+{
+    brb::Rc4Launch c = rc4_args(BRB_RC4_KIND_FRAME, states, payload, frames, offsets, lengths, nullptr, n);
+    c.salts = salts;
+    c.ooffs = frame_offsets;
+    return rc4_batch(c, false, "NULL states, payload, offsets, lengths, salts, frames or frame_offsets", flags, hip_stream);
+}
+
+int BRB_RC4MD5_OpenBatch(BRB_RC4_State *states, const void *frames, void *out, const uint64_t *offsets,
+                         const uint32_t *lengths, uint64_t n, uint8_t *valid, unsigned flags, void *hip_stream)
+{
+    brb::Rc4Launch c = rc4_args(BRB_RC4_KIND_OPEN, states, frames, out, offsets, lengths, nullptr, n);
+    c.valid = valid;
+    return rc4_batch(c, false, "NULL states, frames, out, offsets, lengths or valid", flags, hip_stream);
+}
+
+int BRB_RC4_CryptListBatch(BRB_RC4_State *states, const void *in, void *out, const uint64_t *buf_offsets,
+                           const uint32_t *buf_lengths, const uint64_t *stream_first_buf, uint64_t n, unsigned flags,
+                           void *hip_stream)
+{
+    return rc4_batch(rc4_args(BRB_RC4_KIND_CRYPT, states, in, out, buf_offsets, buf_lengths, stream_first_buf, n), true,
+                     "NULL states, in, out, buf_offsets, buf_lengths or stream_first_buf", flags, hip_stream);
+}
+
+int BRB_RC4MD5_FrameListBatch(BRB_RC4_State *states, const void *payload, const uint64_t *buf_offsets,
+                              const uint32_t *buf_lengths, const uint64_t *salts, void *frames, const uint64_t *frame_offsets,
+                              const uint64_t *stream_first_buf, uint64_t n, unsigned flags, void *hip_stream)
+{
+    brb::Rc4Launch c = rc4_args(BRB_RC4_KIND_FRAME, states, payload, frames, buf_offsets, buf_lengths, stream_first_buf, n);
+    c.salts = salts;
+    c.ooffs = frame_offsets;
+    return rc4_batch(c, true, "NULL states, payload, buf_offsets, buf_lengths, salts, frames, frame_offsets or stream_first_buf",
+                     flags, hip_stream);
+}
+
+int BRB_RC4MD5_OpenListBatch(BRB_RC4_State *states, const void *frames, void *out, const uint64_t *buf_offsets,
+                             const uint32_t *buf_lengths, const uint64_t *stream_first_buf, uint64_t n, uint8_t *valid,
+                             unsigned flags, void *hip_stream)
+{
+    brb::Rc4Launch c = rc4_args(BRB_RC4_KIND_OPEN, states, frames, out, buf_offsets, buf_lengths, stream_first_buf, n);
+    c.valid = valid;
+    return rc4_batch(c, true, "NULL states, frames, out, buf_offsets, buf_lengths, stream_first_buf or valid", flags,
+                     hip_stream);
 }
 
 int BRB_Blowfish_EncryptBatch(const BRB_BLOWFISH_CTX *ctx, unsigned long *words, uint64_t n_blocks, unsigned flags,

@@ -88,42 +88,45 @@ hipError_t launch_b64_encode(const uint8_t *in, const uint64_t *offs, const uint
 hipError_t launch_b64_decode(const uint8_t *in, const uint64_t *offs, const uint32_t *lens, uint64_t n, uint8_t *out,
                              const uint64_t *ooffs, uint32_t *olens, uint64_t mean_len, hipStream_t s);
 
-// RC4 (rc4_kernels.hip): 264-byte BRB_RC4_State records, updated in place.  Stream i uses
-// states[sidx ? sidx[i] : i] (sidx: a connection table, the transform batcher's indirection).
-// ooffs: output offsets (nullptr = the input offsets, out mirrors in)
-// sector_out: write whole aligned 64-byte sectors (brb_io::SectorSnk); the default for HBM and host
-// outputs alike since the session-4 generator (rc4_kernels.hip); false = per-stream 16-byte pieces (Snk)
-hipError_t launch_rc4_crypt(uint8_t *states, const uint8_t *in, uint8_t *out, const uint64_t *offs,
-                            const uint32_t *lens, uint64_t n, hipStream_t s, const uint32_t *sidx = nullptr,
-                            const uint64_t *ooffs = nullptr, bool sector_out = true);
-hipError_t launch_rc4md5_frame(uint8_t *states, const uint8_t *payload, const uint64_t *offs, const uint32_t *lens,
-                               const uint64_t *salts, uint8_t *frames, const uint64_t *foffs, uint64_t n,
-                               hipStream_t s, const uint32_t *sidx = nullptr);
-hipError_t launch_rc4md5_open(uint8_t *states, const uint8_t *in, uint8_t *out, const uint64_t *offs,
-                              const uint32_t *lens, uint64_t n, uint8_t *valid, hipStream_t s,
-                              const uint32_t *sidx = nullptr, const uint64_t *ooffs = nullptr);
-
-// RC4 over a buffer list per stream (rc4_list_kernels.hip): stream i loads states[sidx ? sidx[i] : i]
-// once, walks buffers first[i] .. first[i + 1] - 1 (first: n + 1 non-decreasing entries) in order, each
-// exactly as the launcher above treats its one buffer, and stores the state once.  offs, lens, ooffs,
-// salts, foffs and valid are indexed by buffer.  Lone-wave kernels: no pair fault word is involved.
-hipError_t launch_rc4_crypt_list(uint8_t *states, const uint8_t *in, uint8_t *out, const uint64_t *offs,
-                                 const uint32_t *lens, const uint64_t *first, uint64_t n, hipStream_t s,
-                                 const uint32_t *sidx = nullptr, const uint64_t *ooffs = nullptr);
-hipError_t launch_rc4md5_frame_list(uint8_t *states, const uint8_t *payload, const uint64_t *offs, const uint32_t *lens,
-                                    const uint64_t *salts, uint8_t *frames, const uint64_t *foffs,
-                                    const uint64_t *first, uint64_t n, hipStream_t s, const uint32_t *sidx = nullptr);
-hipError_t launch_rc4md5_open_list(uint8_t *states, const uint8_t *in, uint8_t *out, const uint64_t *offs,
-                                   const uint32_t *lens, const uint64_t *first, uint64_t n, uint8_t *valid,
-                                   hipStream_t s, const uint32_t *sidx = nullptr, const uint64_t *ooffs = nullptr);
-// Streams of mixed kind in one launch (rc4_mixed_kernels.hip): stream i is walked as the list launcher of
-// kind[i] (BRB_RC4_KIND_*) walks it.  Every buffer has its input offset offs[k] in `in` and its output
-// offset ooffs[k] in `out`; salts is read for FRAME buffers only, valid written for OPEN buffers only
-// (either may be nullptr when no stream is of that kind).  Lone waves: no pair fault word.
-hipError_t launch_rc4_mixed_list(uint8_t *states, const uint8_t *kind, const uint8_t *in, uint8_t *out,
-                                 const uint64_t *offs, const uint32_t *lens, const uint64_t *ooffs, const uint64_t *salts,
-                                 const uint64_t *first, uint64_t n, uint8_t *valid, hipStream_t s,
-                                 const uint32_t *sidx = nullptr);
+// RC4, RC4+MD5 frame and RC4+MD5 open (rc4_kernels.hip, rc4_list_kernels.hip, rc4_mixed_kernels.hip): one
+// descriptor for every launch of the family.  Which kernel runs follows from the fields that are set:
+//   kinds           the mixed kernel: stream i is walked as the list kernel of kinds[i] walks it
+//   first, no kinds the list kernel of `kind`: a buffer list per stream
+//   neither         the single-buffer kernels of `kind` (wave pair or lone wave, by the test options)
+// The list and mixed kernels and the lone single-buffer kernels are lone waves: no pair fault word is
+// involved.  The wave-pair kernels report into the word armed on the launching thread (pair_fault.h).
+struct Rc4Launch {
+    int kind = BRB_RC4_KIND_CRYPT;     // one BRB_RC4_KIND_* for the whole launch (not read when kinds is set)
+    const uint8_t *kinds = nullptr;    // a BRB_RC4_KIND_* per stream; non-NULL selects the mixed kernel
+    uint8_t *states = nullptr;         // 264-byte BRB_RC4_State records, updated in place
+    const uint32_t *sidx = nullptr;    // stream i uses states[sidx ? sidx[i] : i] (a connection table, the
+                                       // transform batcher's indirection)
+    const uint8_t *in = nullptr;       // inputs: buffer k = in[offs[k] .. + lens[k])
+    uint8_t *out = nullptr;            // outputs (frames for FRAME: lens[k] + BRB_RC4MD5_HEADER bytes each)
+    const uint64_t *offs = nullptr;    // offs, lens, ooffs, salts and valid are indexed by buffer
+    const uint32_t *lens = nullptr;
+    const uint64_t *ooffs = nullptr;   // output offsets in `out`; NULL = out mirrors in (offs), allowed for
+                                       // CRYPT and OPEN without kinds; FRAME: the frame offsets
+    const uint64_t *salts = nullptr;   // read for FRAME buffers only
+    const uint64_t *first = nullptr;   // stream i owns buffers first[i] .. first[i + 1] - 1 (n + 1 non-decreasing
+                                       // entries): its state is loaded once, the buffers walked in order, each
+                                       // as a single-buffer launch treats its one buffer, the state stored once.
+                                       // NULL = one buffer per stream, buffer i = stream i
+    uint64_t n = 0;                    // streams
+    uint8_t *valid = nullptr;          // written for OPEN buffers only
+    bool sector_out = true;            // single-buffer lone CRYPT: write whole aligned 64-byte sectors
+                                       // (brb_io::SectorSnk), the default for HBM and host outputs alike since
+                                       // the session-4 generator (rc4_kernels.hip); false = per-stream 16-byte
+                                       // pieces (Snk)
+};
+hipError_t launch_rc4_single(const Rc4Launch &l, hipStream_t s);   // rc4_kernels.hip
+hipError_t launch_rc4_list(const Rc4Launch &l, hipStream_t s);     // rc4_list_kernels.hip
+hipError_t launch_rc4_mixed(const Rc4Launch &l, hipStream_t s);    // rc4_mixed_kernels.hip
+// the one entry point of the callers
+inline hipError_t launch_rc4(const Rc4Launch &l, hipStream_t s)
+{
+    return l.kinds ? launch_rc4_mixed(l, s) : l.first ? launch_rc4_list(l, s) : launch_rc4_single(l, s);
+}
 
 // Key setup (keysetup_kernels.hip): key i = keys[koffs[i] .. + klens[i]).
 // RC4: the zeroed-then-BRB_RC4_Init state of key i is written (all 264 bytes) to states[slots ? slots[i] : i],

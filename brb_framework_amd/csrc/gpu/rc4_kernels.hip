@@ -677,63 +677,49 @@ inline unsigned grid_for(uint64_t n) { return unsigned((n + kWave - 1) / kWave);
 
 namespace brb {
 
-hipError_t launch_rc4_crypt(uint8_t *states, const uint8_t *in, uint8_t *out, const uint64_t *offs,
-                            const uint32_t *lens, uint64_t n, hipStream_t s, const uint32_t *sidx,
-                            const uint64_t *ooffs, bool sector_out)
+hipError_t launch_rc4_single(const Rc4Launch &l, hipStream_t s)
 {
+    const uint64_t n = l.n;
     if (n == 0)
         return hipSuccess;
-    // test option "rc4_sector" = 0/1 forces the sink for A/B measurements and tests
-    const int force = brb_opt::get(brb_opt::kRc4Sector);
-    if (force >= 0)
-        sector_out = force == 1;
-    if (brb_opt::get(brb_opt::kRc4CryptPair) != 0 && force < 0) {
-        if (brb_opt::get(brb_opt::kPairStall) != 0)
-            rc4_crypt_pair_kernel<true><<<grid_for(n), 2 * kWave, 0, s>>>(states, in, out, offs, lens, n, sidx, ooffs,
-                                                                          brb::pair_fault_word());
+    const bool stall = brb_opt::get(brb_opt::kPairStall) != 0;
+    if (l.kind == BRB_RC4_KIND_CRYPT) {
+        // test option "rc4_sector" = 0/1 forces the sink for A/B measurements and tests
+        const int force = brb_opt::get(brb_opt::kRc4Sector);
+        const bool sector_out = force >= 0 ? force == 1 : l.sector_out;
+        if (brb_opt::get(brb_opt::kRc4CryptPair) != 0 && force < 0) {
+            if (stall)
+                rc4_crypt_pair_kernel<true><<<grid_for(n), 2 * kWave, 0, s>>>(l.states, l.in, l.out, l.offs, l.lens, n, l.sidx,
+                                                                              l.ooffs, brb::pair_fault_word());
+            else
+                rc4_crypt_pair_kernel<false><<<grid_for(n), 2 * kWave, 0, s>>>(l.states, l.in, l.out, l.offs, l.lens, n, l.sidx,
+                                                                               l.ooffs, brb::pair_fault_word());
+        } else if (sector_out)
+            rc4_crypt_kernel<true><<<grid_for(n), kWave, 0, s>>>(l.states, l.in, l.out, l.offs, l.lens, n, l.sidx, l.ooffs);
         else
-            rc4_crypt_pair_kernel<false><<<grid_for(n), 2 * kWave, 0, s>>>(states, in, out, offs, lens, n, sidx, ooffs,
-                                                                           brb::pair_fault_word());
-    } else if (sector_out)
-        rc4_crypt_kernel<true><<<grid_for(n), kWave, 0, s>>>(states, in, out, offs, lens, n, sidx, ooffs);
-    else
-        rc4_crypt_kernel<false><<<grid_for(n), kWave, 0, s>>>(states, in, out, offs, lens, n, sidx, ooffs);
-    return hipGetLastError();
-}
-
-hipError_t launch_rc4md5_frame(uint8_t *states, const uint8_t *payload, const uint64_t *offs, const uint32_t *lens,
-                               const uint64_t *salts, uint8_t *frames, const uint64_t *foffs, uint64_t n,
-                               hipStream_t s, const uint32_t *sidx)
-{
-    if (n == 0)
-        return hipSuccess;
-    if (brb_opt::get(brb_opt::kRc4Pair) != 0) {
-        if (brb_opt::get(brb_opt::kPairStall) != 0)
-            rc4md5_frame_pair_kernel<true><<<grid_for(n), 2 * kWave, 0, s>>>(states, payload, offs, lens, salts, frames,
-                                                                             foffs, n, sidx, brb::pair_fault_word());
+            rc4_crypt_kernel<false><<<grid_for(n), kWave, 0, s>>>(l.states, l.in, l.out, l.offs, l.lens, n, l.sidx, l.ooffs);
+        return hipGetLastError();
+    }
+    const bool pair = brb_opt::get(brb_opt::kRc4Pair) != 0;
+    if (l.kind == BRB_RC4_KIND_FRAME) {
+        if (pair && stall)
+            rc4md5_frame_pair_kernel<true><<<grid_for(n), 2 * kWave, 0, s>>>(l.states, l.in, l.offs, l.lens, l.salts, l.out,
+                                                                             l.ooffs, n, l.sidx, brb::pair_fault_word());
+        else if (pair)
+            rc4md5_frame_pair_kernel<false><<<grid_for(n), 2 * kWave, 0, s>>>(l.states, l.in, l.offs, l.lens, l.salts, l.out,
+                                                                              l.ooffs, n, l.sidx, brb::pair_fault_word());
         else
-            rc4md5_frame_pair_kernel<false><<<grid_for(n), 2 * kWave, 0, s>>>(states, payload, offs, lens, salts, frames,
-                                                                              foffs, n, sidx, brb::pair_fault_word());
-    } else
-        rc4md5_frame_kernel<<<grid_for(n), kWave, 0, s>>>(states, payload, offs, lens, salts, frames, foffs, n, sidx);
-    return hipGetLastError();
-}
-
-hipError_t launch_rc4md5_open(uint8_t *states, const uint8_t *in, uint8_t *out, const uint64_t *offs,
-                              const uint32_t *lens, uint64_t n, uint8_t *valid, hipStream_t s, const uint32_t *sidx,
-                              const uint64_t *ooffs)
-{
-    if (n == 0)
-        return hipSuccess;
-    if (brb_opt::get(brb_opt::kRc4Pair) != 0) {
-        if (brb_opt::get(brb_opt::kPairStall) != 0)
-            rc4md5_open_pair_kernel<true><<<grid_for(n), 2 * kWave, 0, s>>>(states, in, out, offs, lens, n, valid, sidx,
-                                                                            ooffs, brb::pair_fault_word());
+            rc4md5_frame_kernel<<<grid_for(n), kWave, 0, s>>>(l.states, l.in, l.offs, l.lens, l.salts, l.out, l.ooffs, n, l.sidx);
+    } else {
+        if (pair && stall)
+            rc4md5_open_pair_kernel<true><<<grid_for(n), 2 * kWave, 0, s>>>(l.states, l.in, l.out, l.offs, l.lens, n, l.valid,
+                                                                            l.sidx, l.ooffs, brb::pair_fault_word());
+        else if (pair)
+            rc4md5_open_pair_kernel<false><<<grid_for(n), 2 * kWave, 0, s>>>(l.states, l.in, l.out, l.offs, l.lens, n, l.valid,
+                                                                             l.sidx, l.ooffs, brb::pair_fault_word());
         else
-            rc4md5_open_pair_kernel<false><<<grid_for(n), 2 * kWave, 0, s>>>(states, in, out, offs, lens, n, valid, sidx,
-                                                                             ooffs, brb::pair_fault_word());
-    } else
-        rc4md5_open_kernel<<<grid_for(n), kWave, 0, s>>>(states, in, out, offs, lens, n, valid, sidx, ooffs);
+            rc4md5_open_kernel<<<grid_for(n), kWave, 0, s>>>(l.states, l.in, l.out, l.offs, l.lens, n, l.valid, l.sidx, l.ooffs);
+    }
     return hipGetLastError();
 }
 

@@ -17,6 +17,8 @@
 // so no protocol fault can occur.  A stream without buffers stores the state it loaded (the same
 // 264 bytes: Gen::store drops the byte started ahead).  An empty buffer forms no address that is
 // read or written (BlockSrc / BlockSrcW / Snk with n = 0).
+//
+// Launched through brb::Rc4Launch (brb_kernels.h): a descriptor with `first` set and no `kinds`.
 #include "brb_kernels.h"
 #include "rc4_block.h"
 #include "rc4_device.h"
@@ -141,38 +143,23 @@ inline unsigned grid_for(uint64_t n) { return unsigned((n + kWave - 1) / kWave);
 
 namespace brb {
 
-hipError_t launch_rc4_crypt_list(uint8_t *states, const uint8_t *in, uint8_t *out, const uint64_t *offs,
-                                 const uint32_t *lens, const uint64_t *first, uint64_t n, hipStream_t s,
-                                 const uint32_t *sidx, const uint64_t *ooffs)
+hipError_t launch_rc4_list(const Rc4Launch &l, hipStream_t s)
 {
+    const uint64_t n = l.n;
     if (n == 0)
         return hipSuccess;
+    if (l.kind == BRB_RC4_KIND_FRAME)
+        rc4md5_frame_list_kernel<<<grid_for(n), kWave, 0, s>>>(l.states, l.in, l.offs, l.lens, l.salts, l.out, l.ooffs, l.first, n,
+                                                               l.sidx);
+    else if (l.kind == BRB_RC4_KIND_OPEN)
+        rc4md5_open_list_kernel<<<grid_for(n), kWave, 0, s>>>(l.states, l.in, l.out, l.offs, l.lens, l.first, n, l.valid, l.sidx,
+                                                              l.ooffs);
     // cooperative block loads unless test option "rc4_list_coop" = 0 (16 384 x k x 1500 B, tools/conn_list_ab.py:
     // k = 2 216.3 -> 213.3 us, k = 4 528.8 -> 522.1 us, k = 8 804.4 -> 784.0 us; k = 1 within the spread)
-    if (brb_opt::get(brb_opt::kRc4ListCoop) != 0)
-        rc4_crypt_list_kernel<true><<<grid_for(n), kWave, 0, s>>>(states, in, out, offs, lens, first, n, sidx, ooffs);
+    else if (brb_opt::get(brb_opt::kRc4ListCoop) != 0)
+        rc4_crypt_list_kernel<true><<<grid_for(n), kWave, 0, s>>>(l.states, l.in, l.out, l.offs, l.lens, l.first, n, l.sidx, l.ooffs);
     else
-        rc4_crypt_list_kernel<false><<<grid_for(n), kWave, 0, s>>>(states, in, out, offs, lens, first, n, sidx, ooffs);
-    return hipGetLastError();
-}
-
-hipError_t launch_rc4md5_frame_list(uint8_t *states, const uint8_t *payload, const uint64_t *offs, const uint32_t *lens,
-                                    const uint64_t *salts, uint8_t *frames, const uint64_t *foffs,
-                                    const uint64_t *first, uint64_t n, hipStream_t s, const uint32_t *sidx)
-{
-    if (n == 0)
-        return hipSuccess;
-    rc4md5_frame_list_kernel<<<grid_for(n), kWave, 0, s>>>(states, payload, offs, lens, salts, frames, foffs, first, n, sidx);
-    return hipGetLastError();
-}
-
-hipError_t launch_rc4md5_open_list(uint8_t *states, const uint8_t *in, uint8_t *out, const uint64_t *offs,
-                                   const uint32_t *lens, const uint64_t *first, uint64_t n, uint8_t *valid,
-                                   hipStream_t s, const uint32_t *sidx, const uint64_t *ooffs)
-{
-    if (n == 0)
-        return hipSuccess;
-    rc4md5_open_list_kernel<<<grid_for(n), kWave, 0, s>>>(states, in, out, offs, lens, first, n, valid, sidx, ooffs);
+        rc4_crypt_list_kernel<false><<<grid_for(n), kWave, 0, s>>>(l.states, l.in, l.out, l.offs, l.lens, l.first, n, l.sidx, l.ooffs);
     return hipGetLastError();
 }
 

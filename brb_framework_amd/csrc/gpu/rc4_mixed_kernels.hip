@@ -16,6 +16,8 @@
 // and open lanes, which are most of a mixed round, would lose the second workgroup they have in
 // their own list kernels.  Lone waves only: no partner wave, no wait, no atomics, so no protocol
 // fault can occur.
+//
+// Launched through brb::Rc4Launch (brb_kernels.h): a descriptor with `kinds` set.
 #include "brb_kernels.h"
 #include "rc4_block.h"
 #include "rc4_device.h"
@@ -69,14 +71,12 @@ __global__ __launch_bounds__(kWave) void rc4_mixed_list_kernel(uint8_t *__restri
 
 namespace brb {
 
-hipError_t launch_rc4_mixed_list(uint8_t *states, const uint8_t *kind, const uint8_t *in, uint8_t *out,
-                                 const uint64_t *offs, const uint32_t *lens, const uint64_t *ooffs, const uint64_t *salts,
-                                 const uint64_t *first, uint64_t n, uint8_t *valid, hipStream_t s, const uint32_t *sidx)
+hipError_t launch_rc4_mixed(const Rc4Launch &l, hipStream_t s)
 {
-    if (n == 0)
+    if (l.n == 0)
         return hipSuccess;
-    rc4_mixed_list_kernel<<<unsigned((n + kWave - 1) / kWave), kWave, 0, s>>>(states, kind, in, out, offs, lens, ooffs, salts,
-                                                                              first, n, valid, sidx);
+    rc4_mixed_list_kernel<<<unsigned((l.n + kWave - 1) / kWave), kWave, 0, s>>>(l.states, l.kinds, l.in, l.out, l.offs, l.lens,
+                                                                                l.ooffs, l.salts, l.first, l.n, l.valid, l.sidx);
     return hipGetLastError();
 }
 

@@ -6,7 +6,7 @@
 // one H2D copy, one kernel per direction and sub-round, one D2H copy, and hands every result back
 // in submission order.  The connections' RC4 states (CommEvCryptoInfo's read and write
 // BRB_RC4_State, libbrb_ev_comm.h:206-236) stay resident in HBM; the kernels address them through a
-// connection table (launch_rc4_* `sidx`).
+// connection table (brb::Rc4Launch's `sidx`, brb_kernels.h).
 //
 // Ordering: a connection's buffers in one direction form one RC4 stream, so a round may hold at
 // most one of them per sub-round; the k-th buffer of a connection in a round runs in sub-round k.
@@ -804,7 +804,7 @@ static size_t collect(BRB_TransformBatcher *b, Round &R, std::vector<Item> *stal
 // Where the kernels of a direction read and write, and where the host finds the results: one choice
 // by (zero-copy, algo, op), taken by launch_groups() and by deliver_round().
 struct Where {
-    enum Kind { CRYPT, FRAME, OPEN } kind;
+    enum Kind { CRYPT = BRB_RC4_KIND_CRYPT, FRAME = BRB_RC4_KIND_FRAME, OPEN = BRB_RC4_KIND_OPEN } kind;
     uint8_t *in, *out, *valid;   // device bases of the inputs, the outputs and the valid flags
     const uint8_t *h_out;        // the host's view of `out` (copy mode: once the D2H copies have landed)
     bool at_out_off;             // outputs lie at Item::out_off (the kernel takes ooffs), else they mirror in_off
@@ -867,34 +867,26 @@ static int launch_groups(BRB_TransformBatcher *b, Round &R, size_t *vpos)
         const uint64_t *oo = w.at_out_off ? ooffs : nullptr;   // crypt and open: nullptr = out mirrors in
         if (int64_t(gi) == b->fault_launch)
             return fail_hip("kernel launch (injected fault)", hipErrorLaunchFailure);
-        hipError_t e;
-        if (b->mixed) {   // the round's one group: a valid flag per buffer, written for the open buffers
+        const bool by_list = b->mixed || b->lists;   // a buffer list per connection, else a buffer per stream
+        brb::Rc4Launch l;
+        l.kind = w.kind;
+        l.kinds = b->mixed ? R.d_meta + g.o_kind : nullptr;   // a mixed round: its one group, a kind per stream
+        l.states = b->d_states;
+        l.sidx = sidx;
+        l.in = w.in;
+        l.out = w.out;
+        l.offs = offs;
+        l.lens = lens;
+        l.ooffs = oo;                                // frame and mixed groups always lie at_out_off
+        l.salts = salts;
+        l.first = by_list ? first : nullptr;
+        l.n = by_list ? g.streams : g.count;
+        if (b->mixed || w.kind == Where::OPEN) {     // a valid flag per buffer, written for the open buffers
             R.group_valid[gi] = *vpos;
-            e = brb::launch_rc4_mixed_list(b->d_states, R.d_meta + g.o_kind, w.in, w.out, offs, lens, ooffs, salts, first,
-                                           g.streams, w.valid + *vpos, s, sidx);
-            *vpos += g.count;
-            if (e != hipSuccess)
-                return fail_hip("kernel launch", e);
-            continue;
-        }
-        switch (w.kind) {
-        case Where::CRYPT:
-            e = b->lists ? brb::launch_rc4_crypt_list(b->d_states, w.in, w.out, offs, lens, first, g.streams, s, sidx, oo)
-                         : brb::launch_rc4_crypt(b->d_states, w.in, w.out, offs, lens, g.count, s, sidx, oo);
-            break;
-        case Where::FRAME:
-            e = b->lists ? brb::launch_rc4md5_frame_list(b->d_states, w.in, offs, lens, salts, w.out, ooffs, first,
-                                                         g.streams, s, sidx)
-                         : brb::launch_rc4md5_frame(b->d_states, w.in, offs, lens, salts, w.out, ooffs, g.count, s, sidx);
-            break;
-        default:
-            R.group_valid[gi] = *vpos;
-            e = b->lists ? brb::launch_rc4md5_open_list(b->d_states, w.in, w.out, offs, lens, first, g.streams,
-                                                        w.valid + *vpos, s, sidx, oo)
-                         : brb::launch_rc4md5_open(b->d_states, w.in, w.out, offs, lens, g.count, w.valid + *vpos, s, sidx, oo);
+            l.valid = w.valid + *vpos;
             *vpos += g.count;
         }
-        if (e != hipSuccess)
+        if (const hipError_t e = brb::launch_rc4(l, s); e != hipSuccess)
             return fail_hip("kernel launch", e);
     }
     return BRB_BATCH_OK;

@@ -45,7 +45,7 @@ M = _sibling("rc4_model")
 RAGGED = _sibling("test_rc4").RAGGED
 
 IN_GAP, OUT_FILL = 0xA5, 0x5A
-# the four routes of launch_rc4_crypt: wave pair, one wave with the launcher's sink, one wave with
+# the four routes of a single-buffer CRYPT launch (brb::launch_rc4_single, brb_kernels.h): wave pair, one wave with the launcher's sink, one wave with
 # the per-stream sink, one wave with the sector sink
 ROUTES = [("rc4_pair", 1), ("rc4_pair", 0), ("rc4_sector", 0), ("rc4_sector", 1)]
 ROUTE_IDS = [f"{k}={v}" for k, v in ROUTES]
